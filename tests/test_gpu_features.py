@@ -790,7 +790,7 @@ def test_bench_n2_rehearsal_on_one_gpu():
     import json, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MMGEN_BENCH_ONE_GPU_DRYRUN="1")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--tile-nx", "24",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--tile-nx", "24",
                         "--tile-nz", "24", "--cpu-side", "12"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -800,6 +800,43 @@ def test_bench_n2_rehearsal_on_one_gpu():
     assert line["halo_bytes_received_per_step_all_ranks"] > 0
     assert line["parity_spot_check"] == "bit-exact"
     assert "roofline" in line and "cpu_baseline" in line and line["scaling"] == "weak"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(gen, tmp_path):
+    """A plain bench.py run (no --full) on a 24 x 24-chunk tile: --steps sets the timed steps, the line carries ms_per_step = timed
+    seconds / steps and none of the --full records, and --dump-outputs writes float32 / float64 arrays of at most 64 MB that ARE the
+    step's outputs: the per-chunk sums over the whole tile equal those of the same rectangle generated here, the sampled chunks' too."""
+    import json, subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--tile-nx", "24",
+                        "--tile-nz", "24", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["unit"] == "chunks/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(line["ms_per_step"] - 1000 * line["timed_seconds"] / 3) <= 1000 * 0.0005 / 3 + 0.0001     # timed_seconds is rounded to 1 ms, ms_per_step to 0.1 us
+    assert abs(line["value"] - 576 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+    for k in ("roofline", "kernels_ms", "serial_pass", "cpu_baseline", "parity_spot_check", "cpp_host", "streaming", "baseline_configs", "tiles_bit_exact"):
+        assert k not in line, k
+    got = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ["blocks", "blocks_sum_per_chunk", "hf", "hf_sum_per_chunk"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 * 10 ** 6
+    ref = gen.generate_region(-12, -12, 24, 24)
+    rb, rh = np_(ref["blocks"]), np_(ref["hf"])
+    assert np.array_equal(got["blocks_sum_per_chunk"], rb.sum(1, dtype=np.float64))
+    np.testing.assert_allclose(got["hf_sum_per_chunk"], rh.sum(1, dtype=np.float64), rtol=1e-12)     # float64 sums of 256 floats, order free
+    k = got["blocks"].shape[0]
+    assert 0 < k <= 576 and got["hf"].shape == (k, 256) and got["blocks"].shape == (k, rb.shape[1])
+    # the sample: k distinct chunks in ascending tile order, every voxel and every height of each
+    pos = 0
+    for i in range(k):
+        while pos < 576 and not np.array_equal(rb[pos], got["blocks"][i]):
+            pos += 1
+        assert pos < 576, f"sampled chunk {i} is no chunk of the tile (after the chunks matched so far)"
+        assert np.array_equal(rh[pos].view(np.uint32), got["hf"][i].view(np.uint32)), f"heights of sampled chunk {i} = tile chunk {pos}"
+        pos += 1
 
 
 # ------------------------------------------------------------------------------------------------ stage DAG == serial schedule

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer aid: run bench.py (arguments passed through) and print the headline, the serial pass and the per-kernel milliseconds only."""
 import json, subprocess, sys
-r = subprocess.run([sys.executable, "bench.py", "--cpu-side", "0"] + sys.argv[1:], capture_output=True, text=True)
+r = subprocess.run([sys.executable, "bench.py", "--full", "--cpu-side", "0"] + sys.argv[1:], capture_output=True, text=True)
 line = [l for l in r.stdout.splitlines() if l.startswith('{"metric')]
 if not line:
     print(r.stdout[-2000:], r.stderr[-2000:]); sys.exit(1)
