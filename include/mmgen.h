@@ -270,6 +270,53 @@ int mmgen_mesh_fill_capped(const uint8_t* d_blocks, const int32_t* d_chunk_idx, 
                            const uint32_t* d_column_verts, const uint64_t* d_vert_offset, uint64_t capacity_verts, mmgen_vertex* d_verts, uint32_t* d_idx,
                            void* stream);
 
+/* ---- ray casting over device-resident chunks -------------------------------------------------------------------------------
+ * The reference's only consumer of a generated chunk is OptixRenderer::buildChunkAccel (RT-core hardware).  Here line of sight, block
+ * picking and a headless camera run against the blocks where they lie: d_blocks [*][98304] (a region's output, a pool of chunk slots),
+ * d_grid [grid_h][grid_w] = index into d_blocks of the chunk at grid cell (cx, cz), -1 = absent.
+ *
+ * THE TRAVERSAL CONTRACT (results are a pure function of the inputs; the kernels' skip structure returns exactly this):
+ *   A ray is (o, d), six f32, in GRID-LOCAL block coordinates: x in [0, 16 grid_w), z in [0, 16 grid_h), y = world y (f32 stays exact at
+ *   far world positions).  d need not be normalised.  The ray is INVALID (voxel 0, t 0, face 6) unless every component is finite, o lies in
+ *   the grid's xz rectangle, o.y in [-1024, 1408), d is not all zero and 1.0f / d_a is finite for every d_a != 0.
+ *   Setup: inv_a = 1.0f / d_a (correctly rounded) for d_a != 0; an axis with d_a == 0 never steps.  v = floor(o), t = 0, face = 6 (none).
+ *   EXAMINE v, in this order:
+ *     v outside the xz rectangle                                   -> LEFT_GRID
+ *     v.y < 0 with d_y <= 0, or v.y >= 384 with d_y >= 0           -> LEFT_GRID
+ *     any other v.y outside [0, 384)                               -> air
+ *     d_grid[v.z >> 4][v.x >> 4] == -1                             -> ABSENT_CHUNK (at the first voxel inside that cell)
+ *     block = d_blocks[chunk][v.y + 384 ((v.x & 15) + 16 (v.z & 15))]; its class in stop_mask -> HIT (block reported), else air
+ *   A status ends the ray and reports v, t, face (block = 0 unless HIT).  So a ray that starts inside a stopping block is a HIT with
+ *   t = 0, face = 6.  On air, STEP - non-incremental, from the integer voxel, nothing accumulated:
+ *     for every axis with d_a != 0: p_a = v_a + (d_a > 0), t_a = ((float)p_a - o_a) * inv_a      (two roundings, no fused multiply-add)
+ *     a = the axis with the smallest t_a, ties to the lowest axis index (x, y, z)
+ *     t_a > t_max -> MISS_TMAX, reporting the voxel the ray stands in, t = t_max, face = 6
+ *     otherwise v_a += sign(d_a), t = t_a, face = the dirVecs index (+z 0, +x 1, -z 2, -x 3, +y 4, -y 5) of the outward normal of the
+ *     face entered (a step towards +x enters through the -x face: 3), and EXAMINE again.
+ *   stop_mask: bit set over the mesher's block classes (MMGEN_RAY_OPAQUE 1, _SEMI 2, _TRANSPARENT 4, _XSHAPED 8); 0 or > 15 is
+ *   hipErrorInvalidValue, as are a t_max that is negative or not finite, null pointers and grid sides outside [1, 16384].
+ *   flags: MMGEN_RAY_NO_SKIP walks exactly as written above, one voxel per step (testing, and pricing the skip structure);
+ *   MMGEN_RAY_COUNT_VISITS replaces hit.voxel by {blocks read, boxes classified, brick masks read} (status, t, face, block unchanged).
+ *
+ * mmgen_ray_occupancy builds the skip structure of n chunks for ONE stop_mask: d_occupancy [*][MMGEN_RAY_OCCUPANCY_BYTES], indexed like
+ * d_blocks (chunk d_chunk_idx[i], or i when d_chunk_idx is NULL, writes its own 200 bytes: a pool refreshes only the slots that changed).
+ * Per chunk: u64 whose bit sy says that 16^3 section sy holds a stopping block, then per section a u64 over its 4^3 bricks, bit
+ * by + 4 (bx + 4 bz).  mmgen_raycast / _camera must be given the occupancy of the same blocks and the same stop_mask; every chunk the grid
+ * names must have been built.  Nothing is allocated; all calls are asynchronous on `stream`.
+ *
+ * mmgen_raycast: d_rays [n][6] (o, d), d_hits [n].
+ * mmgen_raycast_camera: d_hits [height][width]; pixel (i, j) (column i, row j, row 0 on top) casts the ray o = eye,
+ *     d_a = (F_a + sx * R_a) + sy * U_a,    sx = ((float)i + 0.5f) * (2.0f / (float)width) - 1.0f,   sy = 1.0f - ((float)j + 0.5f) * (2.0f / (float)height)
+ * in f32 without fused multiply-add, where the basis is computed ONCE on the host in double and rounded to f32:
+ *     f = forward / sqrt(forward . forward),  r = f x up,  r /= sqrt(r . r),  u = r x f   (dot products summed x, y, z)
+ *     F = (float)f,  R = (float)(r * (tan(0.5 * fov_y) * ((double)width / (double)height))),  U = (float)(u * tan(0.5 * fov_y))
+ * so a camera image equals mmgen_raycast on rays built from this formula, record for record. */
+int mmgen_ray_occupancy(const uint8_t* d_blocks, const int32_t* d_chunk_idx, int n, unsigned stop_mask, uint8_t* d_occupancy, void* stream);
+int mmgen_raycast(const uint8_t* d_blocks, const int32_t* d_grid, int grid_w, int grid_h, const uint8_t* d_occupancy, unsigned stop_mask, unsigned flags,
+                  const float* d_rays, int n, float t_max, mmgen_ray_hit* d_hits, void* stream);
+int mmgen_raycast_camera(const uint8_t* d_blocks, const int32_t* d_grid, int grid_w, int grid_h, const uint8_t* d_occupancy, unsigned stop_mask, unsigned flags,
+                         const mmgen_camera* cam, float t_max, mmgen_ray_hit* d_hits, void* stream);
+
 /* ---- region wire format (the reference has none) ---------------------------------------------
  * A chunk's 98 304 block ids as per-column run-length pairs: u16 runsOfColumn[256], then for each column (x + 16 z, the blocks[]
  * order) its runs as (u8 blockId, u8 length - 1), 1 .. 256 voxels per pair.  512 + 2 R bytes per chunk (typically 5 - 9 KB).

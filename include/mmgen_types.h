@@ -59,6 +59,34 @@ typedef struct mmgen_vertex {                /* Vertex, src/rendering/structs.hp
     uint64_t material;                       /* Mats: 0 DIFFUSE, 1 WATER, 2 CRYSTAL, 3 SMOOTH_MICRO, 4 MICRO, 5 ROUGH_MICRO */
 } mmgen_vertex;
 
+/* ---- ray casting (mmgen.h "ray casting over device-resident chunks"; the reference has none: its chunks go to RT cores) ---- */
+typedef struct mmgen_ray_hit {               /* 20 bytes */
+    int32_t voxel[3];                        /* grid-local block x, world y, grid-local block z */
+    float t;                                 /* ray parameter of the plane crossed last (o + t d); 0 at the start voxel; t_max for MISS_TMAX */
+    uint8_t block;                           /* block id for HIT, else 0 */
+    uint8_t face;                            /* dirVecs index (+z, +x, -z, -x, +y, -y) of the outward normal of the face entered; 6 = none */
+    uint8_t status;                          /* MMGEN_RAY_HIT ... */
+    uint8_t pad;                             /* 0 */
+} mmgen_ray_hit;
+enum { MMGEN_RAY_HIT, MMGEN_RAY_MISS_TMAX, MMGEN_RAY_LEFT_GRID, MMGEN_RAY_ABSENT_CHUNK, MMGEN_RAY_INVALID };
+#define MMGEN_RAY_FACE_NONE 6
+/* stop_mask bits = the mesher's block classes (transparency of mm_blockdata.cuh); AIR belongs to none; 15 = any non-air block */
+#define MMGEN_RAY_OPAQUE 1u
+#define MMGEN_RAY_SEMI 2u
+#define MMGEN_RAY_TRANSPARENT 4u
+#define MMGEN_RAY_XSHAPED 8u
+/* flags (debug): walk voxel by voxel without the skip structure; report visit counts in place of the voxel */
+#define MMGEN_RAY_NO_SKIP 1u
+#define MMGEN_RAY_COUNT_VISITS 2u
+#define MMGEN_RAY_OCCUPANCY_BYTES 200        /* per chunk: u64 section mask (bit sy, 24 used), then 24 x u64 brick masks, bit = by + 4 (bx + 4 bz) */
+typedef struct mmgen_camera {                /* pinhole camera in the rays' coordinates */
+    float eye[3];
+    float forward[3];                        /* need not be normalised */
+    float up[3];                             /* not parallel to forward */
+    float fov_y;                             /* vertical field of view, radians, in (0, pi) */
+    int32_t width, height;                   /* pixels */
+} mmgen_camera;
+
 typedef struct mmgen_feature_placement {     /* biome.hpp:195-200: feature@0, pos@4, canReplaceBlocks@16 */
     uint8_t feature;
     uint8_t pad0[3];

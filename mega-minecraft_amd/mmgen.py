@@ -288,6 +288,59 @@ class MMGen:
             raise ValueError("malformed packed chunk")
         return out
 
+    # ------------------------------------------------------------------ ray casting over device-resident chunks (include/mmgen.h)
+    RAY_HIT, RAY_MISS_TMAX, RAY_LEFT_GRID, RAY_ABSENT_CHUNK, RAY_INVALID = range(5)
+    RAY_NO_SKIP, RAY_COUNT_VISITS = 1, 2
+    RAY_HIT_DTYPE = [("voxel", "<i4", 3), ("t", "<f4"), ("block", "u1"), ("face", "u1"), ("status", "u1"), ("pad", "u1")]      # mmgen_ray_hit
+
+    def ray_occupancy(self, blocks, stop_mask=15, chunk_idx=None, out=None):
+        """Skip structure of the chunks of `blocks` (uint8 [slots, 98304]) for one stop_mask -> uint8 [slots, 200], indexed like blocks.
+        chunk_idx (int32 device tensor): only these slots are (re)built, into `out`."""
+        t = self.torch
+        vp = ctypes.c_void_p
+        self.lib.mmgen_ray_occupancy.argtypes = [vp, vp, ctypes.c_int, ctypes.c_uint, vp, vp]
+        occ = out if out is not None else t.zeros((blocks.shape[0], 200), dtype=t.uint8, device=self.device)
+        n = blocks.shape[0] if chunk_idx is None else chunk_idx.shape[0]
+        self._check(self.lib.mmgen_ray_occupancy(self._p(blocks), self._p(chunk_idx), n, stop_mask, self._p(occ), self._stream()), "mmgen_ray_occupancy")
+        return occ
+
+    def raycast(self, blocks, grid, occ, rays, stop_mask=15, t_max=4096.0, flags=0):
+        """grid: int32 [grid_h, grid_w] chunk index into blocks or -1; rays: float32 [n, 6] (o, d) in grid-local block coordinates, on the
+        device.  Returns the hit records as an int32 [n, 5] device tensor; ray_hits() views them as numpy records."""
+        t = self.torch
+        vp, i32, u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint
+        self.lib.mmgen_raycast.argtypes = [vp, vp, i32, i32, vp, u32, u32, vp, i32, ctypes.c_float, vp, vp]
+        assert grid.dtype == t.int32 and rays.dtype == t.float32 and rays.shape[1] == 6 and grid.is_contiguous() and rays.is_contiguous()
+        n = rays.shape[0]
+        hits = self._empty((n, 5), t.int32)
+        self._check(self.lib.mmgen_raycast(self._p(blocks), self._p(grid), grid.shape[1], grid.shape[0], self._p(occ), stop_mask, flags, self._p(rays), n,
+                                           t_max, self._p(hits), self._stream()), "mmgen_raycast")
+        return hits
+
+    def render_view(self, blocks, grid, occ, eye, forward, up=(0.0, 1.0, 0.0), fov_y=1.0, width=640, height=360, stop_mask=15, t_max=4096.0, flags=0):
+        """One primary ray per pixel of a pinhole camera (mmgen_raycast_camera) -> int32 [height, width, 5] hit records on the device."""
+        t = self.torch
+
+        class Camera(ctypes.Structure):
+            _fields_ = [("eye", ctypes.c_float * 3), ("forward", ctypes.c_float * 3), ("up", ctypes.c_float * 3), ("fov_y", ctypes.c_float),
+                        ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+        f3 = ctypes.c_float * 3
+        cam = Camera(f3(*eye), f3(*forward), f3(*up), fov_y, width, height)
+        vp, i32, u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint
+        self.lib.mmgen_raycast_camera.argtypes = [vp, vp, i32, i32, vp, u32, u32, ctypes.POINTER(Camera), ctypes.c_float, vp, vp]
+        assert grid.dtype == t.int32 and grid.is_contiguous()
+        hits = self._empty((height, width, 5), t.int32)
+        self._check(self.lib.mmgen_raycast_camera(self._p(blocks), self._p(grid), grid.shape[1], grid.shape[0], self._p(occ), stop_mask, flags,
+                                                  ctypes.byref(cam), t_max, self._p(hits), self._stream()), "mmgen_raycast_camera")
+        return hits
+
+    @classmethod
+    def ray_hits(cls, hits):
+        """The int32 [..., 5] tensor of raycast / render_view as a numpy record array [...] of mmgen_ray_hit."""
+        import numpy as np
+        a = hits.cpu().numpy()
+        return np.ascontiguousarray(a).view(np.dtype(cls.RAY_HIT_DTYPE)).reshape(a.shape[:-1])
+
     # ------------------------------------------------------------------ region fast path (all stages, device resident)
     EROSION, FEATURES, DECORATORS = 1, 2, 4
 
