@@ -270,6 +270,43 @@ int mmgen_mesh_fill_capped(const uint8_t* d_blocks, const int32_t* d_chunk_idx, 
                            const uint32_t* d_column_verts, const uint64_t* d_vert_offset, uint64_t capacity_verts, mmgen_vertex* d_verts, uint32_t* d_idx,
                            void* stream);
 
+/* ---- greedy-merged compact quad mesh -----------------------------------------------------------------------------------
+ * A second mesher with its own contract: coplanar, adjacent faces of ONE block id merged into rectangles, one 64-bit record per quad
+ * (mmgen_types.h "quad record") for vertex pulling.  d_blocks / d_chunk_idx / d_neighbor_idx exactly as in mmgen_mesh_count.  The quad
+ * stream of a chunk is a pure function of its blocks, its four neighbours' blocks and which neighbours are present; the kernels return
+ * exactly this stream, in this order.
+ *
+ * FACE SET F = the display rule of mmgen_mesh_* (chunk.cu:1906-1928) over the block table's classes AIR, OPAQUE, SEMI, TRANSPARENT,
+ * X_SHAPED (ids >= MMB_NUM_BLOCKS count as OPAQUE); directions in dirVecs order +z 0, +x 1, -z 2, -x 3, +y 4, -y 5:
+ *   an X-shaped block has no faces, it emits one record of kind 6;
+ *   opaque or semi-transparent block: face d is in F iff the neighbour's class is not OPAQUE;
+ *   transparent block: face d is in F iff the neighbour is AIR or SEMI;
+ *   a horizontal neighbour outside the chunk is read from the neighbour chunk when present; when it is absent the face is NOT in F;
+ *   below y = 0 and above y = 383 the neighbour is AIR.
+ * PLANES: a face belongs to plane (d, p) with rows r and fast axis q:
+ *   d in {0, 2}: p = z, r = x, q = y;     d in {1, 3}: p = x, r = z, q = y;     d in {4, 5}: p = y, r = z, q = x.
+ * GREEDY RULE per plane: visit the cells with r ascending, then q ascending.  At the first cell (r0, q0) in F and not yet covered, of block
+ * id b: L = the largest length such that every cell (r0, q0 .. q0+L-1) is in F, uncovered and of id b; W = the largest count such that for
+ * every row r0 .. r0+W-1 all cells (r, q0 .. q0+L-1) are in F, uncovered and of id b; emit one quad of W rows x L cells and mark them
+ * covered.  Faces of different block ids never share a quad, even within one class.  Nothing merges across a chunk border.
+ * ORDER of a chunk's records: the planes with d ascending, then p ascending, each in emission order; then the kind-6 records in ascending
+ * voxel index y + 384 (x + 16 z).  Each (d, p) is one group and the kind-6 records one more: 64 + 768 + 1 = MMGEN_QUAD_GROUPS, group index
+ * 16 d + p for d < 4, 64 + 384 (d - 4) + p for d >= 4, 832 for kind 6.
+ * NOT REPRESENTED: the per-face random uv rotation and flip of the reference's Vertex stream.  A consumer tiles the block's texture over the
+ * quad; the material follows from the block id as in the vertex mesher (mesh_material, chunk.cu:1797-1829).
+ *
+ *   mmgen_mesh_quads_count: d_group_quads [n][MMGEN_QUAD_GROUPS] and d_chunk_quads [n] receive the record counts.
+ *   mmgen_mesh_quads_fill : writes chunk i's records at d_quads[d_quad_offset[i] ...]; d_quad_offset = exclusive prefix of d_chunk_quads
+ *                           (mmgen_mesh_offsets computes it on the device unchanged: count -> offsets -> fill needs no host read).  A chunk
+ *                           whose records would end beyond capacity_quads writes nothing; UINT64_MAX = uncapped, 0 is hipErrorInvalidValue.
+ * Nothing is allocated; all calls are asynchronous on `stream`. */
+#define MMGEN_QUAD_GROUPS 833
+int mmgen_mesh_quads_count(const uint8_t* d_blocks, const int32_t* d_chunk_idx, const int32_t* d_neighbor_idx, int n,
+                           uint32_t* d_group_quads /*[n][MMGEN_QUAD_GROUPS]*/, uint32_t* d_chunk_quads /*[n]*/, void* stream);
+int mmgen_mesh_quads_fill(const uint8_t* d_blocks, const int32_t* d_chunk_idx, const int32_t* d_neighbor_idx, int n,
+                          const uint32_t* d_group_quads, const uint64_t* d_quad_offset, uint64_t capacity_quads,
+                          uint64_t* d_quads, void* stream);
+
 /* ---- ray casting over device-resident chunks -------------------------------------------------------------------------------
  * The reference's only consumer of a generated chunk is OptixRenderer::buildChunkAccel (RT-core hardware).  Here line of sight, block
  * picking and a headless camera run against the blocks where they lie: d_blocks [*][98304] (a region's output, a pool of chunk slots),

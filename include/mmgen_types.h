@@ -59,6 +59,16 @@ typedef struct mmgen_vertex {                /* Vertex, src/rendering/structs.hp
     uint64_t material;                       /* Mats: 0 DIFFUSE, 1 WATER, 2 CRYSTAL, 3 SMOOTH_MICRO, 4 MICRO, 5 ROUGH_MICRO */
 } mmgen_vertex;
 
+/* ---- quad record of the greedy mesher (mmgen.h "greedy-merged compact quad mesh"): one uint64_t per quad ----
+ *   bits  0- 3  x of the min-corner voxel          bits 20-23  dx
+ *   bits  4-12  y of the min-corner voxel          bits 24-32  dy
+ *   bits 13-16  z of the min-corner voxel          bits 33-36  dz
+ *   bits 17-19  kind: 0-5 = direction d            bits 37-44  block id
+ *               (+z +x -z -x +y -y), 6 = X-shaped  bits 45-63  zero
+ * dx, dy, dz are extents minus one; the extent along the normal is 0; a kind-6 record has all extents 0.  The quad is the face, on side d,
+ * of the box [x, x+dx+1) x [y, y+dy+1) x [z, z+dz+1). */
+#define MMGEN_QUAD_KIND_XSHAPED 6
+
 /* ---- ray casting (mmgen.h "ray casting over device-resident chunks"; the reference has none: its chunks go to RT cores) ---- */
 typedef struct mmgen_ray_hit {               /* 20 bytes */
     int32_t voxel[3];                        /* grid-local block x, world y, grid-local block z */

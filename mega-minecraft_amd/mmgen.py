@@ -250,6 +250,59 @@ class MMGen:
                                                     self._p(verts), self._p(idx), self._stream()), "mmgen_mesh_fill_capped")
         return dict(verts=verts, idx=idx, chunk_verts=chv, vert_offset=off, total=int(total.item()))
 
+    # ------------------------------------------------------------------ greedy-merged quad mesh (include/mmgen.h)
+    QUAD_GROUPS = 833
+
+    def mesh_quads(self, blocks, nx=None, nz=None, neighbor_idx=None, chunk_idx=None, capacity_quads=None):
+        """blocks: uint8 [slots, 98304] on the device; chunk_idx (int32 device tensor) picks the chunks to mesh (None = all, in order).
+        Neighbours as in create_vbos: `neighbor_idx` (int32 [n, 4] N E S W index into blocks, -1 = absent), or a z-major nx x nz grid shape
+        (without chunk_idx), or neither (every chunk alone).  capacity_quads=None sizes the buffer from the counts; a given capacity runs
+        count -> mmgen_mesh_offsets -> fill without a host read into a buffer pre-filled with -7, and chunks that would end beyond it are left
+        untouched.  Returns dict(quads int64 [Q or capacity], chunk_quads int32 [n], quad_offset int64 [n], total)."""
+        t = self.torch
+        n = blocks.shape[0] if chunk_idx is None else chunk_idx.shape[0]
+        vp, i32, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
+        self.lib.mmgen_mesh_quads_count.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+        self.lib.mmgen_mesh_quads_fill.argtypes = [vp, vp, vp, i32, vp, vp, u64, vp, vp]
+        self.lib.mmgen_mesh_offsets.argtypes = [vp, i32, vp, vp, vp]
+        if neighbor_idx is None and nx is not None:
+            assert chunk_idx is None, "a grid shape names the neighbours of chunks 0 .. n-1; give neighbor_idx with chunk_idx"
+            c = t.arange(n, dtype=t.int32, device=blocks.device)
+            x, z = c % nx, c // nx
+            neg = t.full_like(c, -1)
+            neighbor_idx = t.stack([t.where(z < nz - 1, c + nx, neg), t.where(x < nx - 1, c + 1, neg), t.where(z > 0, c - nx, neg),
+                                    t.where(x > 0, c - 1, neg)], dim=1).contiguous()
+        groups = self._empty((max(n, 1), self.QUAD_GROUPS), t.int32)
+        chq = self._empty((n,), t.int32)
+        self._check(self.lib.mmgen_mesh_quads_count(self._p(blocks), self._p(chunk_idx), self._p(neighbor_idx), n, self._p(groups), self._p(chq), self._stream()),
+                    "mmgen_mesh_quads_count")
+        if capacity_quads is None:
+            incl = t.cumsum(chq.to(t.int64), 0)
+            off = (incl - chq).contiguous()
+            total = int(incl[-1].item()) if n else 0
+            quads = self._empty((max(total, 1),), t.int64)
+            capacity = 2 ** 64 - 1
+        else:
+            off = self._empty((max(n, 1),), t.int64)[:n]
+            tot = self._empty((1,), t.int64)
+            quads = t.full((capacity_quads,), -7, dtype=t.int64, device=blocks.device)
+            self._check(self.lib.mmgen_mesh_offsets(self._p(chq), n, self._p(off), self._p(tot), self._stream()), "mmgen_mesh_offsets")
+            total, capacity = None, capacity_quads
+        if n:
+            self._check(self.lib.mmgen_mesh_quads_fill(self._p(blocks), self._p(chunk_idx), self._p(neighbor_idx), n, self._p(groups), self._p(off), capacity,
+                                                       self._p(quads), self._stream()), "mmgen_mesh_quads_fill")
+        if total is None:
+            return dict(quads=quads, chunk_quads=chq, quad_offset=off, total=int(tot.item()))
+        return dict(quads=quads[:total], chunk_quads=chq, quad_offset=off, total=total)
+
+    @classmethod
+    def quad_fields(cls, quads):
+        """Decodes quad records (int64 tensor or array) into a dict of numpy fields x, y, z, kind, dx, dy, dz, block (mmgen_types.h)."""
+        import numpy as np
+        q = (quads.cpu().numpy() if hasattr(quads, "cpu") else np.asarray(quads)).astype(np.int64).view(np.uint64)
+        field = lambda shift, bits: ((q >> np.uint64(shift)) & np.uint64((1 << bits) - 1)).astype(np.int32)
+        return dict(x=field(0, 4), y=field(4, 9), z=field(13, 4), kind=field(17, 3), dx=field(20, 4), dy=field(24, 9), dz=field(33, 4), block=field(37, 8))
+
     # ------------------------------------------------------------------ region wire format (run-length pairs per column)
     def pack(self, blocks):
         """blocks uint8 [n, 98304] on the device -> dict(data uint8 [total], chunk_bytes int32 [n], chunk_offset int64 [n])."""
