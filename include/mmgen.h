@@ -354,6 +354,48 @@ int mmgen_raycast(const uint8_t* d_blocks, const int32_t* d_grid, int grid_w, in
 int mmgen_raycast_camera(const uint8_t* d_blocks, const int32_t* d_grid, int grid_w, int grid_h, const uint8_t* d_occupancy, unsigned stop_mask, unsigned flags,
                          const mmgen_camera* cam, float t_max, mmgen_ray_hit* d_hits, void* stream);
 
+/* ---- voxel lighting: sky and block light over device-resident chunks --------------------------------------------------------
+ * The reference gets its illumination from an OptiX path tracer and an emissive texture.  Here every voxel gets the classic pair of
+ * 4-bit values, each dropping by one per step through voxels that are not opaque.  d_blocks, d_grid [grid_h][grid_w] (index into the
+ * chunk slots, -1 = absent) exactly as in mmgen_raycast.  The light is a pure function of the grid's blocks and the emission table.
+ *
+ * THE LIGHT CONTRACT
+ *   Block classes are the mesher's: AIR, OPAQUE, SEMI, TRANSPARENT, X_SHAPED; ids >= MMB_NUM_BLOCKS count as OPAQUE.  e[256] is the
+ *   emission table, values 0..15 (a larger value is taken as 15); NULL selects the default table:
+ *     LAVA, GLOWSTONE, SHROOMLIGHT, SEA_LANTERN 15;  CAVE_VINES_GLOW_MAIN, CAVE_VINES_GLOW_END 14;  MAGENTA_, CYAN_, GREEN_CRYSTAL 10;
+ *     SMALL_ and HANGING_SMALL_ MAGENTA_, CYAN_, GREEN_CRYSTAL 6;  every other id 0     (mmgen_light_default_emission returns it).
+ *   The domain is the voxels of the grid's present chunks.  Everything else - absent cells, cells outside the grid, y < 0, y > 383 - has
+ *   T = 0, emits nothing, is not open and has light 0.
+ *     T(v)     the class of v is not OPAQUE: light passes AIR, SEMI, TRANSPARENT and X_SHAPED alike, at a cost of 1 per step;
+ *     open(v)  v and every voxel above it in its column, up to y = 383, is AIR or X_SHAPED;
+ *     block(v) = max(e[id(v)], T(v) ? max over the 6 face neighbours n of block(n) - 1 : 0), never below 0: an opaque emitter carries its
+ *                own emission and lights its neighbours, an opaque non-emitter is 0;
+ *     sky(v)   = 15 if open(v), else T(v) ? max over the 6 face neighbours n of sky(n) - 1 : 0: water, ice and leaves under the open sky
+ *                get 14, 13, ...
+ *   Both fields are the unique solutions of these equations.  Equivalently, with S_16 = {} and dilate6 = the union of the six shifts:
+ *     S_L = {source >= L} | (T & dilate6(S_L+1)) for L = 15 .. 1 (source = e[id] for block light, 15 on open voxels and 0 elsewhere for sky
+ *     light), and the light of v is the number of L with v in S_L.
+ *   Output: d_light[slot][y + 384 (x + 16 z)] = (sky << 4) | block, laid out and indexed like d_blocks.
+ *   EXACTNESS: the light of a voxel depends only on the blocks within Manhattan distance 14 of it and on the column above it.  So a chunk
+ *   whose 8 neighbours are present has the light of the unbounded world; a chunk next to an absent cell is darker towards it, absent cells
+ *   behave as dark rock.
+ *
+ * mmgen_light_masks derives, per chunk slot, what the lighting reads instead of the blocks (to lighting what mmgen_ray_occupancy is to
+ * rays): d_masks [*][MMGEN_LIGHT_MASK_BYTES], indexed like d_blocks; chunk d_chunk_idx[i] (i when NULL) writes its own record, so a pool
+ * refreshes only the slots whose blocks changed.  d_emission: e[256] on the device, NULL = the default table.  The record has no
+ * capacity on the number of emitters: a lava lake, or a table that makes STONE glow, is legal input.
+ * mmgen_light lights the chunks of the listed grid cells (d_cells [n] = cz * grid_w + cx on the device, NULL = cells 0 .. n-1).  It must be
+ * given the masks of EVERY present chunk of the grid, built with one emission table.  Only the slots of listed cells that are present are
+ * written; every other slot of d_light stays untouched.
+ * Nothing is allocated; all calls are asynchronous on `stream`; n == 0 succeeds without a launch.  Null pointers, grid sides outside
+ * [1, 16384], n < 0, and n beyond grid_w * grid_h when d_cells is NULL are hipErrorInvalidValue.  A d_cells entry outside the grid lives on
+ * the device, where an asynchronous call cannot report it: such an entry is skipped, nothing is written for it. */
+int mmgen_light_default_emission(uint8_t* h_out /*[256], host*/);
+int mmgen_light_masks(const uint8_t* d_blocks, const int32_t* d_chunk_idx, int n, const uint8_t* d_emission /*[256] device, NULL = default*/,
+                      uint8_t* d_masks /*[*][MMGEN_LIGHT_MASK_BYTES], indexed like d_blocks*/, void* stream);
+int mmgen_light(const uint8_t* d_masks, const int32_t* d_grid, int grid_w, int grid_h, const int32_t* d_cells /*[n] grid cells to light, NULL = cells 0..n-1*/,
+                int n, uint8_t* d_light /*[*][98304], indexed like d_blocks*/, void* stream);
+
 /* ---- region wire format (the reference has none) ---------------------------------------------
  * A chunk's 98 304 block ids as per-column run-length pairs: u16 runsOfColumn[256], then for each column (x + 16 z, the blocks[]
  * order) its runs as (u8 blockId, u8 length - 1), 1 .. 256 voxels per pair.  512 + 2 R bytes per chunk (typically 5 - 9 KB).

@@ -97,6 +97,15 @@ typedef struct mmgen_camera {                /* pinhole camera in the rays' coor
     int32_t width, height;                   /* pixels */
 } mmgen_camera;
 
+/* ---- voxel lighting (mmgen_light_masks / mmgen_light, include/mmgen.h) ----
+ * The mask record of a chunk slot, c = x + 16 z, word w = y / 64, bit y % 64:
+ *   u64 [256][6]     at     0   the voxel passes light (its class is not OPAQUE)
+ *   u64 [256][6][4]  at 12288   bit k of the voxel's emission value, k = 0..3
+ *   u16 [256]        at 61440   open height: the lowest y from which the column is AIR / X_SHAPED up to y = 383, 384 = none
+ *   u32 [256]        at 61952   nibble w = OR of the emission values of the column's word w (0 = no emitter in that word) */
+#define MMGEN_LIGHT_MASK_BYTES 62976
+#define MMGEN_LIGHT_MAX 15
+
 typedef struct mmgen_feature_placement {     /* biome.hpp:195-200: feature@0, pos@4, canReplaceBlocks@16 */
     uint8_t feature;
     uint8_t pad0[3];

@@ -21,7 +21,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_feature_placements", "k_gather_placements", "k_apply_features", "k_decorators", "k_feature_box",
     "k_select", "k_ring_need", "k_copy_placements", "k_ring_pack", "k_ring_unpack",
     "k_mesh_count", "k_mesh_fill", "k_pack_count", "k_pack_fill", "k_unpack", "k_erode_rescue",
-    "k_ray_occupancy", "k_raycast", "k_raycast_camera", "k_quads_count", "k_quads_fill"};
+    "k_ray_occupancy", "k_raycast", "k_raycast_camera", "k_quads_count", "k_quads_fill",
+    "k_light_masks", "k_light"};
 
 hipEvent_t get_event()
 {

@@ -394,6 +394,43 @@ class MMGen:
         a = hits.cpu().numpy()
         return np.ascontiguousarray(a).view(np.dtype(cls.RAY_HIT_DTYPE)).reshape(a.shape[:-1])
 
+    # ------------------------------------------------------------------ voxel lighting over device-resident chunks (include/mmgen.h)
+    LIGHT_MASK_BYTES = 62976
+
+    def light_default_emission(self):
+        """The default emission table (include/mmgen.h) as a numpy uint8 [256]."""
+        import numpy as np
+        out = np.zeros(256, np.uint8)
+        self.lib.mmgen_light_default_emission.argtypes = [ctypes.c_void_p]
+        self._check(self.lib.mmgen_light_default_emission(out.ctypes.data), "mmgen_light_default_emission")
+        return out
+
+    def light_masks(self, blocks, chunk_idx=None, emission=None, out=None):
+        """What the lighting reads of the chunks of `blocks` (uint8 [slots, 98304]) -> uint8 [slots, LIGHT_MASK_BYTES], indexed like blocks.
+        chunk_idx (int32 device tensor): only these slots are (re)built, into `out`.  emission: uint8 [256] device tensor, None = default."""
+        t = self.torch
+        vp = ctypes.c_void_p
+        self.lib.mmgen_light_masks.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
+        masks = out if out is not None else t.zeros((blocks.shape[0], self.LIGHT_MASK_BYTES), dtype=t.uint8, device=self.device)
+        n = blocks.shape[0] if chunk_idx is None else chunk_idx.shape[0]
+        assert emission is None or (emission.dtype == t.uint8 and emission.numel() == 256 and emission.is_contiguous())
+        self._check(self.lib.mmgen_light_masks(self._p(blocks), self._p(chunk_idx), n, self._p(emission), self._p(masks), self._stream()), "mmgen_light_masks")
+        return masks
+
+    def light(self, masks, grid, cells=None, out=None):
+        """grid: int32 [grid_h, grid_w] chunk slot or -1; masks: light_masks of every present chunk.  cells (int32 device tensor of grid cell
+        indices cz * grid_w + cx): only these are lit, None = all.  Returns uint8 [slots, 98304] of (sky << 4) | block, indexed like blocks;
+        slots that are not lit keep what `out` held (zero when it is allocated here)."""
+        t = self.torch
+        vp, i32 = ctypes.c_void_p, ctypes.c_int
+        self.lib.mmgen_light.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
+        assert grid.dtype == t.int32 and grid.dim() == 2 and grid.is_contiguous()
+        light = out if out is not None else t.zeros((masks.shape[0], BLOCKS), dtype=t.uint8, device=self.device)
+        n = grid.numel() if cells is None else cells.shape[0]
+        self._check(self.lib.mmgen_light(self._p(masks), self._p(grid), grid.shape[1], grid.shape[0], self._p(cells), n, self._p(light), self._stream()),
+                    "mmgen_light")
+        return light
+
     # ------------------------------------------------------------------ region fast path (all stages, device resident)
     EROSION, FEATURES, DECORATORS = 1, 2, 4
 

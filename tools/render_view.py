@@ -4,6 +4,7 @@ one primary ray per pixel (mmgen_raycast_camera) and one shadow ray per hit towa
 block id, face and shadow, and writes <out>.ppm (binary P6) and <out>.npy (the hit records).  No image library.
 
 usage: tools/render_view.py [--cx 1488 --cz -1110 --nx 8 --nz 8] [--eye surface|cave|x,y,z] [--forward x,y,z] [--size 1280x720] [--out view]
+       tools/render_view.py --light ...   # shade by the light volume (mmgen_light): max(sky, block) / 15 of the voxel in front of the hit face
        tools/render_view.py --measure     # both eyes, skip / no-skip, occupancy build, visits per ray
 Eye and forward are in grid-local block coordinates (x, z from the region's corner, y = world y)."""
 import argparse
@@ -56,6 +57,21 @@ def eye_for(kind, blocks_host, nx, nz):
     if best[1] is None:
         raise SystemExit("no cave below the centre chunks of this region")
     return best[1]
+
+
+def shade_by_light(gen, hits, light, grid):
+    """--light: a hit is shaded by the light volume (mmgen_light) at the voxel in front of the face that was entered, max(sky, block) / 15"""
+    H = gen.ray_hits(hits)
+    hit = H["status"] == gen.RAY_HIT
+    v = H["voxel"][hit] + NORMAL[H["face"][hit]].astype(np.int32)
+    gh, gw = grid.shape
+    inside = (v[:, 0] >= 0) & (v[:, 0] < 16 * gw) & (v[:, 2] >= 0) & (v[:, 2] < 16 * gh) & (v[:, 1] >= 0) & (v[:, 1] < 384)
+    vi = np.where(inside[:, None], v, 0)
+    b = light[grid[vi[:, 2] >> 4, vi[:, 0] >> 4], vi[:, 1] + 384 * ((vi[:, 0] & 15) + 16 * (vi[:, 2] & 15))]
+    level = np.where(inside, np.maximum(b >> 4, b & 15), np.where(v[:, 1] > 383, 15, 0)).astype(np.float32)
+    img = np.broadcast_to(SKY, H.shape + (3,)).copy()
+    img[hit] = palette()[H["block"][hit]] * (level / 15.0)[:, None]
+    return np.clip(img, 0, 255).astype(np.uint8), H
 
 
 def shade(gen, blocks, grid, occ, hits, eye, rays_d, t_max):
@@ -132,6 +148,7 @@ def main():
     ap.add_argument("--eye", default="surface"); ap.add_argument("--forward", default="1,-0.35,0.6")
     ap.add_argument("--fov", type=float, default=1.0); ap.add_argument("--size", default="1280x720")
     ap.add_argument("--out", default="view"); ap.add_argument("--measure", action="store_true")
+    ap.add_argument("--light", action="store_true", help="shade by the light volume (sky and block light) instead of face factor and shadow ray")
     args = ap.parse_args()
     gen = importlib.import_module("mega-minecraft_amd").MMGen(0)
     if args.measure:
@@ -143,7 +160,10 @@ def main():
     eye = eye_for(args.eye, blocks.cpu().numpy(), args.nx, args.nz) if args.eye in ("surface", "cave") else tuple(float(v) for v in args.eye.split(","))
     forward = tuple(float(v) for v in args.forward.split(","))
     hits = gen.render_view(blocks, grid, occ, eye, forward, fov_y=args.fov, width=w, height=h, t_max=4096.0)
-    img, H = shade(gen, blocks, grid, occ, hits, eye, pixel_dirs(forward, (0.0, 1.0, 0.0), args.fov, w, h), 4096.0)
+    if args.light:
+        img, H = shade_by_light(gen, hits, gen.light(gen.light_masks(blocks), grid).cpu().numpy(), grid.cpu().numpy())
+    else:
+        img, H = shade(gen, blocks, grid, occ, hits, eye, pixel_dirs(forward, (0.0, 1.0, 0.0), args.fov, w, h), 4096.0)
     with open(args.out + ".ppm", "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (w, h)); f.write(img.tobytes())
     np.save(args.out + ".npy", H)
