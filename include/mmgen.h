@@ -396,6 +396,49 @@ int mmgen_light_masks(const uint8_t* d_blocks, const int32_t* d_chunk_idx, int n
 int mmgen_light(const uint8_t* d_masks, const int32_t* d_grid, int grid_w, int grid_h, const int32_t* d_cells /*[n] grid cells to light, NULL = cells 0..n-1*/,
                 int n, uint8_t* d_light /*[*][98304], indexed like d_blocks*/, void* stream);
 
+/* ---- section visibility: face connectivity per 16^3 section and the occlusion-culled set of sections an eye can see -----------
+ * The reference culls with OptiX.  Here: per section, which of its six faces are connected through see-through voxels (15 bits), and a
+ * walk of the section graph outward from the eye's section through connected faces that never turns back.  d_blocks, d_chunk_idx exactly
+ * as in mmgen_ray_occupancy and mmgen_light_masks; d_grid as in mmgen_raycast.  Faces are numbered in dirVecs order.
+ *
+ * THE CONNECTIVITY CONTRACT (mmgen_section_connectivity)
+ *   d_conn [*][MMGEN_SECTION_CONN_BYTES], indexed like d_blocks: per chunk slot u16 [24], section sy = y >> 4.  Chunk d_chunk_idx[i] (i when
+ *   NULL) writes its own 48 bytes, every other slot stays untouched.
+ *   A voxel SEES THROUGH iff its class is not OPAQUE: AIR, SEMI, TRANSPARENT and X_SHAPED do, ids >= MMB_NUM_BLOCKS are OPAQUE (the T of
+ *   the lighting).  Face d of a section is the layer of its 256 voxels at local z = 15 (d = 0), x = 15 (1), z = 0 (2), x = 0 (3), y = 15 (4),
+ *   y = 0 (5); an edge voxel belongs to two faces, a corner voxel to three.
+ *   Faces a < b are CONNECTED iff a 6-connected path of see-through voxels, all of them inside the section, has a voxel in layer a and a
+ *   voxel in layer b.  One voxel is a path.  A path that leaves the section and comes back does not count; nothing is read from
+ *   neighbouring chunks.
+ *   The pair (a, b) is bit a (11 - a) / 2 + b - a - 1 of the section's u16: bits 0..14 are (0,1), (0,2) .. (0,5), (1,2) .. (4,5); bit 15 is 0.
+ *   A section without an opaque voxel gives 0x7fff, one without a see-through voxel 0.
+ *   Null d_blocks or d_conn and n < 0 are hipErrorInvalidValue; n == 0 succeeds without a launch.
+ *
+ * THE VISIBLE-SET CONTRACT (mmgen_visible_sections)
+ *   d_conn must hold the record of every present chunk of the window.  The window is the cells with |cx - eye_cx| <= radius and
+ *   |cz - eye_cz| <= radius.  A section is (cx, sy, cz), sy in [-1, 24]; the layers sy = -1 and sy = 24 are virtual.  A window cell outside
+ *   the grid does not exist: nothing steps into it.  A window cell inside the grid that is absent, and every virtual-layer section of a window
+ *   cell inside the grid, is TRANSPARENT: its record reads 0x7fff and it is never reported.
+ *   Let s0 = (eye_cx, eye_sy, eye_cz), E(s) a set of faces of s.  A step from s through its face d to n = s + dirVec(d) is taken iff
+ *     n exists,  the step moves away from the eye on its axis: (n_a - s0_a) * sign(d) > 0 for the axis a of d,  and
+ *     s = s0, or some f in E(s) has the pair (f, d) set in the record of s.
+ *   A taken step puts opposite(d) into E(n) (d ^ 2 for d < 4; 4 and 5 are each other's opposite).  The E are the least sets closed under this
+ *   rule; every step increases the Manhattan distance from s0 by one, so E at distance k depends on E at distance k - 1 only: they are unique.
+ *   d_visible [2 radius + 1][2 radius + 1]: entry (cz - eye_cz + radius)(2 radius + 1) + (cx - eye_cx + radius) has bit sy (0..23) set iff the
+ *   cell is present and E((cx, sy, cz)) is not empty or the section is s0.  Every entry is written; cells outside the grid or absent get 0.
+ *   There is no frustum test (the consumer's), and the eye's section exits through all six faces (no flood from the eye voxel): conservative.
+ *   Null pointers, grid sides outside [1, 16384], an eye cell outside the grid, eye_sy outside [-1, 24] and a radius outside
+ *   [0, MMGEN_VISIBLE_MAX_RADIUS] are hipErrorInvalidValue.
+ *   CONSERVATIVE: a contract ray of mmgen_raycast with stop_mask = MMGEN_RAY_OPAQUE whose origin lies in section s0 with y in [0, 384) walks
+ *   voxels that are 6-connected, monotone on every axis and see-through up to the HIT voxel.  Cut at section borders, that walk is a chain of
+ *   taken steps, so the section of every HIT voxel inside the window is reported.  An eye above y = 383 passes eye_sy = 24, one below 0
+ *   passes -1: both layers see through everywhere and the ray is monotone, so the set stays conservative.
+ * Both calls are asynchronous on `stream` and allocate nothing. */
+int mmgen_section_connectivity(const uint8_t* d_blocks, const int32_t* d_chunk_idx, int n, uint8_t* d_conn /*[*][48], indexed like d_blocks*/,
+                               void* stream);
+int mmgen_visible_sections(const uint8_t* d_conn, const int32_t* d_grid, int grid_w, int grid_h, int eye_cx, int eye_sy, int eye_cz, int radius,
+                           uint32_t* d_visible /*[2 radius + 1][2 radius + 1]*/, void* stream);
+
 /* ---- region wire format (the reference has none) ---------------------------------------------
  * A chunk's 98 304 block ids as per-column run-length pairs: u16 runsOfColumn[256], then for each column (x + 16 z, the blocks[]
  * order) its runs as (u8 blockId, u8 length - 1), 1 .. 256 voxels per pair.  512 + 2 R bytes per chunk (typically 5 - 9 KB).
@@ -429,6 +472,9 @@ int mmgen_debug_tables(float* d_out, int capacity_floats, void* stream);
  * featurePlacement.hpp:147,1110); d_out[box_size x*y*z] in z, x, y order (y fastest), 255 = voxel not claimed. */
 int mmgen_debug_feature_box(int is_cave, int feature, const int32_t* h_feature_pos, int layer_height, const int32_t* h_box_min,
                             const int32_t* h_box_size, uint8_t* d_out, void* stream);
+/* Measuring only: mmgen_section_connectivity that also reports, per chunk slot it writes, the flood rounds it took: d_rounds [*], indexed
+ * like d_blocks. */
+int mmgen_debug_section_rounds(const uint8_t* d_blocks, const int32_t* d_chunk_idx, int n, uint8_t* d_conn, uint32_t* d_rounds, void* stream);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,12 @@ typedef struct mmgen_camera {                /* pinhole camera in the rays' coor
 #define MMGEN_LIGHT_MASK_BYTES 62976
 #define MMGEN_LIGHT_MAX 15
 
+/* ---- section visibility (mmgen_section_connectivity / mmgen_visible_sections, include/mmgen.h) ----
+ * The connectivity record of a chunk slot: u16 [24], one per 16^3 section sy = y >> 4; bit a (11 - a) / 2 + b - a - 1 = faces a < b (dirVecs
+ * order) are connected through see-through voxels inside the section; bit 15 is 0. */
+#define MMGEN_SECTION_CONN_BYTES 48
+#define MMGEN_VISIBLE_MAX_RADIUS 32
+
 typedef struct mmgen_feature_placement {     /* biome.hpp:195-200: feature@0, pos@4, canReplaceBlocks@16 */
     uint8_t feature;
     uint8_t pad0[3];

@@ -431,6 +431,43 @@ class MMGen:
                     "mmgen_light")
         return light
 
+    # ------------------------------------------------------------------ section visibility over device-resident chunks (include/mmgen.h)
+    SECTION_CONN_BYTES = 48
+    VISIBLE_MAX_RADIUS = 32
+
+    def section_connectivity(self, blocks, chunk_idx=None, out=None, rounds=None):
+        """Face connectivity of the 24 sections of the chunks of `blocks` (uint8 [slots, 98304]) -> uint8 [slots, 48] (u16 [24] per slot),
+        indexed like blocks.  chunk_idx (int32 device tensor): only these slots are (re)built, into `out`.  rounds (int32 [slots] device
+        tensor, measuring only): receives the flood rounds of every chunk built."""
+        t = self.torch
+        vp = ctypes.c_void_p
+        self.lib.mmgen_section_connectivity.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+        self.lib.mmgen_debug_section_rounds.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
+        conn = out if out is not None else t.zeros((blocks.shape[0], self.SECTION_CONN_BYTES), dtype=t.uint8, device=self.device)
+        n = blocks.shape[0] if chunk_idx is None else chunk_idx.shape[0]
+        if rounds is not None:
+            assert rounds.dtype == t.int32 and rounds.numel() >= blocks.shape[0] and rounds.is_contiguous()
+            code = self.lib.mmgen_debug_section_rounds(self._p(blocks), self._p(chunk_idx), n, self._p(conn), self._p(rounds), self._stream())
+        else:
+            code = self.lib.mmgen_section_connectivity(self._p(blocks), self._p(chunk_idx), n, self._p(conn), self._stream())
+        self._check(code, "mmgen_section_connectivity")
+        return conn
+
+    def visible_sections(self, conn, grid, eye_section, radius):
+        """grid: int32 [grid_h, grid_w] chunk slot or -1; conn: section_connectivity of every present chunk of the window; eye_section:
+        (cx, sy, cz) with sy in [-1, 24].  Returns uint32 [2 radius + 1, 2 radius + 1]: entry [cz - eye_cz + radius][cx - eye_cx + radius]
+        has bit sy set iff that section has to be drawn."""
+        t = self.torch
+        vp, i32 = ctypes.c_void_p, ctypes.c_int
+        self.lib.mmgen_visible_sections.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+        assert grid.dtype == t.int32 and grid.dim() == 2 and grid.is_contiguous() and conn.dtype == t.uint8 and conn.is_contiguous()
+        cx, sy, cz = (int(v) for v in eye_section)
+        w = 2 * max(int(radius), 0) + 1
+        vis = self._empty((w, w), t.uint32)
+        self._check(self.lib.mmgen_visible_sections(self._p(conn), self._p(grid), grid.shape[1], grid.shape[0], cx, sy, cz, int(radius), self._p(vis),
+                                                    self._stream()), "mmgen_visible_sections")
+        return vis
+
     # ------------------------------------------------------------------ region fast path (all stages, device resident)
     EROSION, FEATURES, DECORATORS = 1, 2, 4
 
