@@ -439,6 +439,60 @@ int mmgen_section_connectivity(const uint8_t* d_blocks, const int32_t* d_chunk_i
 int mmgen_visible_sections(const uint8_t* d_conn, const int32_t* d_grid, int grid_w, int grid_h, int eye_cx, int eye_sy, int eye_cz, int radius,
                            uint32_t* d_visible /*[2 radius + 1][2 radius + 1]*/, void* stream);
 
+/* ---- section-bucketed quad mesh and its draw list -------------------------------------------------------------------------
+ * A third mesher: the greedy quad stream cut at the borders of the 16^3 sections, one 32-bit record per quad (mmgen_types.h "section quad
+ * record"), every section's records one contiguous range - the stream that mmgen_visible_sections can cull.  (Culling the 64-bit stream of
+ * mmgen_mesh_quads_* by the section of a quad's origin is not conservative: its side faces merge along y over the whole column.)
+ * d_blocks / d_chunk_idx / d_neighbor_idx exactly as in mmgen_mesh_quads_count.  The stream of a chunk is a pure function of its blocks, its
+ * four neighbours' blocks and which neighbours are present; the kernels return exactly this stream, in this order.
+ *
+ * FACE SET F: that of mmgen_mesh_quads_*, word for word - the display rule of mmgen_mesh_* (chunk.cu:1906-1928) over the classes AIR,
+ * OPAQUE, SEMI, TRANSPARENT, X_SHAPED (ids >= MMB_NUM_BLOCKS count as OPAQUE); directions in dirVecs order +z 0, +x 1, -z 2, -x 3, +y 4, -y 5:
+ *   an X-shaped block has no faces, it emits one record of kind 6;
+ *   opaque or semi-transparent block: face d is in F iff the neighbour's class is not OPAQUE;
+ *   transparent block: face d is in F iff the neighbour is AIR or SEMI;
+ *   a horizontal neighbour outside the chunk is read from the neighbour chunk when present; when it is absent the face is NOT in F;
+ *   below y = 0 and above y = 383 the neighbour is AIR.
+ * SECTIONS AND PLANES: a section is (chunk, sy), sy = y >> 4.  Per section 96 planes (d, p), p in 0..15, of 16 rows r x 16 cells q:
+ *   d in {0, 2}: p = z, r = x, q = y & 15;     d in {1, 3}: p = x, r = z, q = y & 15;     d in {4, 5}: p = y & 15, r = z, q = x.
+ * GREEDY RULE: that of mmgen_mesh_quads_*, applied to each 16 x 16 plane: visit the cells with r ascending, then q ascending.  At the first
+ * cell (r0, q0) in F and not yet covered, of block id b: L = the largest length such that every cell (r0, q0 .. q0+L-1) is in F, uncovered and
+ * of id b; W = the largest count such that for every row r0 .. r0+W-1 all cells (r, q0 .. q0+L-1) are in F, uncovered and of id b; emit one
+ * quad of W rows x L cells and mark them covered.  Faces of different ids never share a quad.  Nothing merges across a section border or a
+ * chunk border.
+ * ORDER of a chunk's records: sy ascending; inside a section the planes with d ascending, then p ascending, each in emission order; then that
+ * section's kind-6 records in ascending voxel index y + 384 (x + 16 z).  A section's records are therefore one contiguous range.
+ *
+ *   mmgen_mesh_section_quads_count: d_section_quads [n][24] and d_chunk_quads [n] receive the record counts.
+ *   mmgen_mesh_section_quads_fill : d_quad_offset = exclusive prefix of d_chunk_quads (mmgen_mesh_offsets computes it on the device unchanged:
+ *                           count -> offsets -> fill needs no host read).  Section sy of chunk i starts at d_quad_offset[i] + the sum of
+ *                           d_section_quads[i][k], k < sy.  A chunk whose records would end beyond capacity_quads writes nothing; UINT64_MAX =
+ *                           uncapped, 0 is hipErrorInvalidValue.  A section never writes more records than were counted for it: blocks that
+ *                           changed between the two calls cannot make it write outside its range.
+ * n == 0 succeeds without a launch; null pointers and n < 0 are hipErrorInvalidValue.  Nothing is allocated; both calls are asynchronous on
+ * `stream`.
+ *
+ * THE DRAW LIST (mmgen_section_draws): the visible sections that have records, as ranges of d_quads, built on the device.
+ *   d_visible, d_grid, grid_w, grid_h, eye_cx, eye_cz, radius: the output and the arguments of mmgen_visible_sections.  d_mesh_pos [slots]:
+ *   position of a chunk slot in the work list that was meshed (d_section_quads and d_quad_offset are indexed by it, n entries), -1 = not
+ *   meshed; NULL = the slot itself.
+ *   Walk the window entries of d_visible in their stored order (wz major, then wx).  Take each entry whose cell lies in the grid, is present
+ *   with slot s, and has m = d_mesh_pos ? d_mesh_pos[s] : s in [0, n).  For that entry take each sy ascending whose bit is set in the entry
+ *   and whose d_section_quads[m][sy] > 0.  Each such (entry, sy) is one draw: first = the section's start as defined above, count =
+ *   d_section_quads[m][sy], origin = wx | wz << 7 | sy << 14 with wx = cx - eye_cx + radius, wz = cz - eye_cz + radius.
+ *   Draw k is written iff k < capacity_draws.  d_totals[0] = the number of draws, d_totals[1] = the sum of their counts, both over ALL draws,
+ *   not only the written ones: a caller grows the buffer and repeats.  d_draws may be NULL when capacity_draws is 0.
+ *   Other null pointers, n < 0, grid sides outside [1, 16384], an eye cell outside the grid and a radius outside
+ *   [0, MMGEN_VISIBLE_MAX_RADIUS] are hipErrorInvalidValue.  Nothing is allocated; the call is asynchronous on `stream`. */
+int mmgen_mesh_section_quads_count(const uint8_t* d_blocks, const int32_t* d_chunk_idx, const int32_t* d_neighbor_idx, int n,
+                                   uint32_t* d_section_quads /*[n][24]*/, uint32_t* d_chunk_quads /*[n]*/, void* stream);
+int mmgen_mesh_section_quads_fill(const uint8_t* d_blocks, const int32_t* d_chunk_idx, const int32_t* d_neighbor_idx, int n,
+                                  const uint32_t* d_section_quads, const uint64_t* d_quad_offset, uint64_t capacity_quads,
+                                  uint32_t* d_quads, void* stream);
+int mmgen_section_draws(const uint32_t* d_visible, const int32_t* d_grid, int grid_w, int grid_h, int eye_cx, int eye_cz, int radius,
+                        const int32_t* d_mesh_pos /*[slots], NULL = identity*/, const uint32_t* d_section_quads, const uint64_t* d_quad_offset, int n,
+                        uint32_t capacity_draws, mmgen_section_draw* d_draws, uint64_t* d_totals /*[2]*/, void* stream);
+
 /* ---- region wire format (the reference has none) ---------------------------------------------
  * A chunk's 98 304 block ids as per-column run-length pairs: u16 runsOfColumn[256], then for each column (x + 16 z, the blocks[]
  * order) its runs as (u8 blockId, u8 length - 1), 1 .. 256 voxels per pair.  512 + 2 R bytes per chunk (typically 5 - 9 KB).

@@ -112,6 +112,22 @@ typedef struct mmgen_camera {                /* pinhole camera in the rays' coor
 #define MMGEN_SECTION_CONN_BYTES 48
 #define MMGEN_VISIBLE_MAX_RADIUS 32
 
+/* ---- section quad record (mmgen.h "section-bucketed quad mesh"): one uint32_t per quad, coordinates local to the 16^3 section ----
+ *   bits  0- 3  x of the min-corner voxel          bits 15-18  W - 1, the extent along the plane's rows r
+ *   bits  4- 7  y & 15 of the min-corner voxel     bits 19-22  L - 1, the extent along the plane's fast axis q
+ *   bits  8-11  z of the min-corner voxel          bits 23-30  block id
+ *   bits 12-14  kind: 0-5 = direction d            bit  31     zero
+ *               (+z +x -z -x +y -y), 6 = X-shaped
+ * Rows and fast axis per direction: d in {0, 2}: r = x, q = y;  d in {1, 3}: r = z, q = y;  d in {4, 5}: r = z, q = x.  A kind-6 record has
+ * W - 1 = L - 1 = 0.  The section (chunk, sy) is not in the record: it follows from the record's position (mmgen_section_draw.origin). */
+#define MMGEN_SECTIONS_PER_CHUNK 24
+/* one contiguous range of section quad records = one section that has to be drawn (mmgen_section_draws) */
+typedef struct mmgen_section_draw {          /* 16 bytes */
+    uint64_t first;                          /* index of the section's first record in d_quads */
+    uint32_t count;                          /* its records, > 0 */
+    uint32_t origin;                         /* wx | wz << 7 | sy << 14: window cell (cx - eye_cx + radius, cz - eye_cz + radius) and section */
+} mmgen_section_draw;
+
 typedef struct mmgen_feature_placement {     /* biome.hpp:195-200: feature@0, pos@4, canReplaceBlocks@16 */
     uint8_t feature;
     uint8_t pad0[3];

@@ -22,7 +22,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_select", "k_ring_need", "k_copy_placements", "k_ring_pack", "k_ring_unpack",
     "k_mesh_count", "k_mesh_fill", "k_pack_count", "k_pack_fill", "k_unpack", "k_erode_rescue",
     "k_ray_occupancy", "k_raycast", "k_raycast_camera", "k_quads_count", "k_quads_fill",
-    "k_light_masks", "k_light", "k_section_conn", "k_visible_sections"};
+    "k_light_masks", "k_light", "k_section_conn", "k_visible_sections",
+    "k_section_quads_count", "k_section_quads_fill", "k_section_draws"};
 
 hipEvent_t get_event()
 {

@@ -303,6 +303,85 @@ class MMGen:
         field = lambda shift, bits: ((q >> np.uint64(shift)) & np.uint64((1 << bits) - 1)).astype(np.int32)
         return dict(x=field(0, 4), y=field(4, 9), z=field(13, 4), kind=field(17, 3), dx=field(20, 4), dy=field(24, 9), dz=field(33, 4), block=field(37, 8))
 
+    # ------------------------------------------------------------------ section-bucketed quad mesh and its draw list (include/mmgen.h)
+    SECTIONS = 24
+    SECTION_DRAW_DTYPE = [("first", "<u8"), ("count", "<u4"), ("origin", "<u4")]      # mmgen_section_draw
+
+    def mesh_section_quads(self, blocks, nx=None, nz=None, neighbor_idx=None, chunk_idx=None, capacity_quads=None):
+        """The greedy quad mesh cut at the borders of the 16^3 sections, one 32-bit record per quad, every section's records contiguous.
+        Arguments as in mesh_quads, including the capped form (buffer pre-filled with -7, chunks that would end beyond it left untouched).
+        Returns dict(quads int32 [Q or capacity], section_quads int32 [n, 24], chunk_quads int32 [n], quad_offset int64 [n], total)."""
+        t = self.torch
+        n = blocks.shape[0] if chunk_idx is None else chunk_idx.shape[0]
+        vp, i32, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
+        self.lib.mmgen_mesh_section_quads_count.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+        self.lib.mmgen_mesh_section_quads_fill.argtypes = [vp, vp, vp, i32, vp, vp, u64, vp, vp]
+        self.lib.mmgen_mesh_offsets.argtypes = [vp, i32, vp, vp, vp]
+        if neighbor_idx is None and nx is not None:
+            assert chunk_idx is None, "a grid shape names the neighbours of chunks 0 .. n-1; give neighbor_idx with chunk_idx"
+            c = t.arange(n, dtype=t.int32, device=blocks.device)
+            x, z = c % nx, c // nx
+            neg = t.full_like(c, -1)
+            neighbor_idx = t.stack([t.where(z < nz - 1, c + nx, neg), t.where(x < nx - 1, c + 1, neg), t.where(z > 0, c - nx, neg),
+                                    t.where(x > 0, c - 1, neg)], dim=1).contiguous()
+        secq = self._empty((max(n, 1), self.SECTIONS), t.int32)[:n]
+        chq = self._empty((n,), t.int32)
+        self._check(self.lib.mmgen_mesh_section_quads_count(self._p(blocks), self._p(chunk_idx), self._p(neighbor_idx), n, self._p(secq), self._p(chq),
+                                                            self._stream()), "mmgen_mesh_section_quads_count")
+        if capacity_quads is None:
+            incl = t.cumsum(chq.to(t.int64), 0)
+            off = (incl - chq).contiguous()
+            total = int(incl[-1].item()) if n else 0
+            quads = self._empty((max(total, 1),), t.int32)
+            capacity = 2 ** 64 - 1
+        else:
+            off = self._empty((max(n, 1),), t.int64)[:n]
+            tot = self._empty((1,), t.int64)
+            quads = t.full((capacity_quads,), -7, dtype=t.int32, device=blocks.device)
+            self._check(self.lib.mmgen_mesh_offsets(self._p(chq), n, self._p(off), self._p(tot), self._stream()), "mmgen_mesh_offsets")
+            total, capacity = None, capacity_quads
+        if n:
+            self._check(self.lib.mmgen_mesh_section_quads_fill(self._p(blocks), self._p(chunk_idx), self._p(neighbor_idx), n, self._p(secq), self._p(off),
+                                                               capacity, self._p(quads), self._stream()), "mmgen_mesh_section_quads_fill")
+        if total is None:
+            return dict(quads=quads, section_quads=secq, chunk_quads=chq, quad_offset=off, total=int(tot.item()))
+        return dict(quads=quads[:total], section_quads=secq, chunk_quads=chq, quad_offset=off, total=total)
+
+    @classmethod
+    def section_quad_fields(cls, quads):
+        """Decodes section quad records (int32 tensor or array) into a dict of numpy fields x, y (0..15, local to the section), z, kind,
+        w (extent - 1 along the plane's rows), l (extent - 1 along its fast axis), block (mmgen_types.h)."""
+        import numpy as np
+        q = (quads.cpu().numpy() if hasattr(quads, "cpu") else np.asarray(quads)).astype(np.int64) & 0xffffffff
+        field = lambda shift, bits: ((q >> shift) & ((1 << bits) - 1)).astype(np.int32)
+        return dict(x=field(0, 4), y=field(4, 4), z=field(8, 4), kind=field(12, 3), w=field(15, 4), l=field(19, 4), block=field(23, 8))
+
+    def section_draws(self, visible, grid, eye_cell, radius, mesh, mesh_pos=None, capacity=None):
+        """The draw list of a visible set (visible_sections' output for the same grid, eye cell (cx, cz) and radius) over a section mesh (the
+        dict of mesh_section_quads): one (first, count, origin) per visible section that has records, in window order.  mesh_pos: int32
+        [slots] device tensor, position of a chunk slot in the mesh's work list, -1 = not meshed; None = the slot itself.  capacity=None
+        sizes the buffer for every section of the window; a given capacity receives the first `capacity` draws.  The buffer is pre-filled with 0xff bytes
+        and has one guard record behind the capacity.  Returns dict(draws numpy records [min(total, capacity)] of SECTION_DRAW_DTYPE,
+        totals (draws, quads) over all draws, buffer = the device tensor uint8 [capacity + 1, 16])."""
+        import numpy as np
+        t = self.torch
+        vp, i32, u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32
+        self.lib.mmgen_section_draws.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, u32, vp, vp, vp]
+        assert grid.dtype == t.int32 and grid.dim() == 2 and grid.is_contiguous() and visible.is_contiguous()
+        cx, cz = (int(v) for v in eye_cell)
+        w = 2 * max(int(radius), 0) + 1
+        assert visible.numel() == w * w
+        cap = w * w * self.SECTIONS if capacity is None else int(capacity)
+        buf = t.full((cap + 1, 16), 0xff, dtype=t.uint8, device=self.device)
+        totals = self._empty((2,), t.int64)
+        secq, off = mesh["section_quads"], mesh["quad_offset"]
+        self._check(self.lib.mmgen_section_draws(self._p(visible), self._p(grid), grid.shape[1], grid.shape[0], cx, cz, int(radius), self._p(mesh_pos),
+                                                 self._p(secq), self._p(off), secq.shape[0], cap, self._p(buf), self._p(totals), self._stream()),
+                    "mmgen_section_draws")
+        tot = tuple(int(v) for v in totals.cpu().numpy())
+        draws = np.ascontiguousarray(buf.cpu().numpy()).view(np.dtype(self.SECTION_DRAW_DTYPE)).reshape(-1)
+        return dict(draws=draws[:min(tot[0], cap)], totals=tot, buffer=buf)
+
     # ------------------------------------------------------------------ region wire format (run-length pairs per column)
     def pack(self, blocks):
         """blocks uint8 [n, 98304] on the device -> dict(data uint8 [total], chunk_bytes int32 [n], chunk_offset int64 [n])."""

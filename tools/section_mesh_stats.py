@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Size and time of the section-bucketed quad mesh beside the chunk-wide greedy stream (section 6.6) on the 32 x 32-chunk
+region that tools/quad_mesh_stats.py and tools/visibility_stats.py use, all in one process: records and bytes per chunk of both streams, count +
+fill of both meshers, k_section_draws beside k_visible_sections, and for the three eyes of tools/visibility_stats.py the quads that the draw list
+really draws beside the quads of the 64-bit stream whose ORIGIN lies in a visible section (not conservative: section 6.8).  Times are the
+library's own per-kernel profile over the whole region, after a warm-up, median / min / max over the repeats.  MMGEN_LIB selects an A/B build.
+
+usage: tools/section_mesh_stats.py [--cx 1488 --cz -1110 --nx 32 --nz 32 --warmup 5 --reps 30]"""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from quad_mesh_stats import kernel_ms  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cx", type=int, default=1488); ap.add_argument("--cz", type=int, default=-1110)
+    ap.add_argument("--nx", type=int, default=32); ap.add_argument("--nz", type=int, default=32)
+    ap.add_argument("--warmup", type=int, default=5); ap.add_argument("--reps", type=int, default=30)
+    a = ap.parse_args()
+    pkg = importlib.import_module("mega-minecraft_amd")
+    gen = pkg.MMGen(0)
+    t = gen.torch
+    blocks = gen.generate_region(a.cx, a.cz, a.nx, a.nz)["blocks"]
+    n = a.nx * a.nz
+    grid = t.arange(n, dtype=t.int32, device=gen.device).reshape(a.nz, a.nx)
+    print(f"library {pkg.LIB_PATH}")
+
+    greedy = gen.mesh_quads(blocks, a.nx, a.nz)
+    sec = gen.mesh_section_quads(blocks, a.nx, a.nz)
+    gq, sq = greedy["chunk_quads"].cpu().numpy(), sec["chunk_quads"].cpu().numpy()
+    secq = sec["section_quads"].cpu().numpy()
+    f = gen.section_quad_fields(sec["quads"])
+    area = ((f["w"] + 1) * (f["l"] + 1))[f["kind"] < 6]
+    print(f"region {a.nx}x{a.nz} chunks at ({a.cx}, {a.cz}): greedy stream {gq.mean():.1f} records per chunk (max {gq.max()}) = {8.0 * gq.mean():.0f} bytes; "
+          f"section stream {sq.mean():.1f} records per chunk (max {sq.max()}) = {4.0 * sq.mean():.0f} bytes; records x {sq.sum() / gq.sum():.3f}, bytes x "
+          f"{4.0 * sq.sum() / (8.0 * gq.sum()):.3f}; {area.mean():.2f} unit faces per section quad; {np.count_nonzero(secq)} of {24 * n} sections have records, "
+          f"largest section {secq.max()}")
+
+    # the eyes of tools/visibility_stats.py: the middle column of the middle chunk, two voxels above its ground; its lowest see-through voxel; above the world
+    ecx, ecz = a.nx // 2, a.nz // 2
+    radius = max(ecx, a.nx - 1 - ecx, ecz, a.nz - 1 - ecz)
+    if radius > gen.VISIBLE_MAX_RADIUS:
+        sys.exit(f"radius {radius} beyond {gen.VISIBLE_MAX_RADIUS}: choose a smaller region")
+    T = gen.light_masks(blocks)[ecz * a.nx + ecx].cpu().numpy()[:12288].view(np.uint64).reshape(256, 6)[8 + 16 * 8]
+    through = np.array([(int(T[y >> 6]) >> (y & 63)) & 1 for y in range(384)], bool)
+    ground = int(np.max(np.nonzero(~through)[0]))
+    below = np.nonzero(through[:ground])[0]
+    eyes = [("surface", min(ground + 2, 383) >> 4), ("above the world", 24)]
+    if len(below):
+        eyes.insert(1, (f"cave (y = {int(below[0])})", int(below[0]) >> 4))
+    conn = gen.section_connectivity(blocks)
+    q = gen.quad_fields(greedy["quads"])
+    chunk_of = np.repeat(np.arange(n), gq)
+    for name, sy in eyes:
+        vis = gen.visible_sections(conn, grid, (ecx, sy, ecz), radius)
+        d = gen.section_draws(vis, grid, (ecx, ecz), radius, sec)
+        cells = vis.cpu().numpy()[radius - ecz:radius - ecz + a.nz, radius - ecx:radius - ecx + a.nx].reshape(-1)
+        by_origin = int(np.count_nonzero((cells[chunk_of] >> (q["y"] >> 4).astype(np.uint32)) & 1))
+        print(f"eye {name}, section ({ecx}, {sy}, {ecz}), radius {radius}: {d['totals'][0]} draws, {d['totals'][1]} of {sec['total']} section quads drawn "
+              f"({100.0 * d['totals'][1] / max(sec['total'], 1):.1f} %) = {4 * d['totals'][1]} bytes; greedy stream by origin {by_origin} of {greedy['total']} "
+              f"({100.0 * by_origin / max(greedy['total'], 1):.1f} %) = {8 * by_origin} bytes")
+
+    vis = gen.visible_sections(conn, grid, (ecx, eyes[0][1], ecz), radius)
+    for name, fn, kernels in (("section mesher", lambda: gen.mesh_section_quads(blocks, a.nx, a.nz), ("k_section_quads_count", "k_section_quads_fill")),
+                              ("  its count", lambda: gen.mesh_section_quads(blocks, a.nx, a.nz), ("k_section_quads_count",)),
+                              ("greedy mesher", lambda: gen.mesh_quads(blocks, a.nx, a.nz), ("k_quads_count", "k_quads_fill")),
+                              ("  its count", lambda: gen.mesh_quads(blocks, a.nx, a.nz), ("k_quads_count",)),
+                              ("section mesher", lambda: gen.mesh_section_quads(blocks, a.nx, a.nz), ("k_section_quads_count", "k_section_quads_fill")),
+                              ("greedy mesher", lambda: gen.mesh_quads(blocks, a.nx, a.nz), ("k_quads_count", "k_quads_fill")),
+                              ("draw list", lambda: gen.section_draws(vis, grid, (ecx, ecz), radius, sec), ("k_section_draws",)),
+                              ("visible set", lambda: gen.visible_sections(conn, grid, (ecx, eyes[0][1], ecz), radius), ("k_visible_sections",))):
+        med, lo, hi = kernel_ms(gen, fn, kernels, a.warmup, a.reps)
+        print(f"{name:14s} median {med:.3f} ms (min {lo:.3f}, max {hi:.3f}) over {a.reps} runs = {1e3 * med / n:.2f} us per chunk")
+
+
+if __name__ == "__main__":
+    main()
