@@ -493,6 +493,44 @@ int mmgen_section_draws(const uint32_t* d_visible, const int32_t* d_grid, int gr
                         const int32_t* d_mesh_pos /*[slots], NULL = identity*/, const uint32_t* d_section_quads, const uint64_t* d_quad_offset, int n,
                         uint32_t capacity_draws, mmgen_section_draw* d_draws, uint64_t* d_totals /*[2]*/, void* stream);
 
+/* ---- lit section quad mesh: per-quad light, light-aware greedy merge ------------------------------------------------------
+ * The section-bucketed stream with flat lighting: the light of a face is the light of the voxel in front of it, two faces share a quad only if
+ * they share the block id AND that light, and every record carries its light in a parallel byte stream.  With it the dense light volume
+ * (98 304 bytes per chunk) is a transient like the class planes: the draw list of mmgen_section_draws delivers lit geometry as it stands.
+ * d_blocks / d_chunk_idx / d_neighbor_idx exactly as in mmgen_mesh_section_quads_count.  d_light [*][98304] is indexed and laid out like
+ * d_blocks - normally the output of mmgen_light, but any bytes are legal input.  The caller must have lit every listed chunk and every
+ * present neighbour.
+ *
+ * FACE LIGHT: F, directions, sections and planes are exactly those of mmgen_mesh_section_quads_*.  For a face (v, d) of F
+ *     FL(v, d) = L(v + dirVec(d)) & light_mask
+ *   L inside the chunk is read from the chunk's own slot of d_light;
+ *   a horizontal neighbour outside the chunk is read from the slot d_neighbor_idx names (a face towards an absent neighbour is not in F, so
+ *   that light is never needed);
+ *   above y = 383 L is MMGEN_LIGHT_ABOVE = 0xF0 (sky 15, block 0); below y = 0 L is 0x00;
+ *   for a kind-6 record (X-shaped block) FL = L(v) & light_mask, the voxel's own light.
+ * GREEDY RULE: that of mmgen_mesh_section_quads_*, applied to each 16 x 16 plane: visit the cells with r ascending, then q ascending.  At the
+ * first cell (r0, q0) in F and not yet covered, of block id b and face light FL(r0, q0): L = the largest length such that every cell
+ * (r0, q0 .. q0+L-1) is in F, uncovered, of id b and of that face light; W = the largest count such that for every row r0 .. r0+W-1 all
+ * cells (r, q0 .. q0+L-1) are in F, uncovered, of id b and of that face light; emit one quad of W rows x L cells and mark them covered.
+ * Nothing merges across a section border or a chunk border.  ORDER, the section ranges, the record format, count -> mmgen_mesh_offsets -> fill,
+ * the capacity rule and "a section never writes more records than were counted for it" are those of mmgen_mesh_section_quads_*.
+ * The stream of a chunk is a pure function of its blocks and light, its four neighbours' blocks and light, which neighbours are present,
+ * and light_mask.  With light_mask == 0 the records equal those of mmgen_mesh_section_quads_fill exactly and every light byte is 0; 0xF0 merges
+ * by sky light alone, 0x0F by block light alone.
+ *
+ *   mmgen_mesh_lit_section_quads_count: d_section_quads [n][24] and d_chunk_quads [n] receive the record counts.
+ *   mmgen_mesh_lit_section_quads_fill : d_quads holds the section quad record of mmgen_types.h, bit for bit; d_quad_light[k] is the face light
+ *                           of record k, a parallel byte stream over the same indices.  Offsets, mmgen_section_draws and a vertex puller's
+ *                           decode work on these counts and offsets unchanged.  A chunk whose records would end beyond capacity_quads
+ *                           writes NEITHER array.  Blocks, light and light_mask must be those of the count.
+ * n == 0 succeeds without a launch; null pointers (d_light among them) and n < 0 are hipErrorInvalidValue, as is capacity_quads == 0.
+ * Nothing is allocated; both calls are asynchronous on `stream`. */
+int mmgen_mesh_lit_section_quads_count(const uint8_t* d_blocks, const uint8_t* d_light, const int32_t* d_chunk_idx, const int32_t* d_neighbor_idx, int n,
+                                       uint8_t light_mask, uint32_t* d_section_quads /*[n][24]*/, uint32_t* d_chunk_quads /*[n]*/, void* stream);
+int mmgen_mesh_lit_section_quads_fill(const uint8_t* d_blocks, const uint8_t* d_light, const int32_t* d_chunk_idx, const int32_t* d_neighbor_idx, int n,
+                                      uint8_t light_mask, const uint32_t* d_section_quads, const uint64_t* d_quad_offset, uint64_t capacity_quads,
+                                      uint32_t* d_quads, uint8_t* d_quad_light, void* stream);
+
 /* ---- region wire format (the reference has none) ---------------------------------------------
  * A chunk's 98 304 block ids as per-column run-length pairs: u16 runsOfColumn[256], then for each column (x + 16 z, the blocks[]
  * order) its runs as (u8 blockId, u8 length - 1), 1 .. 256 voxels per pair.  512 + 2 R bytes per chunk (typically 5 - 9 KB).

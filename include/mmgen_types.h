@@ -105,6 +105,7 @@ typedef struct mmgen_camera {                /* pinhole camera in the rays' coor
  *   u32 [256]        at 61952   nibble w = OR of the emission values of the column's word w (0 = no emitter in that word) */
 #define MMGEN_LIGHT_MASK_BYTES 62976
 #define MMGEN_LIGHT_MAX 15
+#define MMGEN_LIGHT_ABOVE 0xF0u               /* the light above y = 383: sky 15, block 0 (mmgen_mesh_lit_section_quads_*) */
 
 /* ---- section visibility (mmgen_section_connectivity / mmgen_visible_sections, include/mmgen.h) ----
  * The connectivity record of a chunk slot: u16 [24], one per 16^3 section sy = y >> 4; bit a (11 - a) / 2 + b - a - 1 = faces a < b (dirVecs

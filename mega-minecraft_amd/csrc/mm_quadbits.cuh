@@ -57,6 +57,23 @@ MM_DEV void column_equal_below(const uint4* __restrict__ me, uint64_t eq[6])
     eq[0] &= ~1ull;                                        // nothing below y = 0
 }
 
+// ---- additions for the lit section mesher (mmgen_lit_section_quads.hip): the same byte equality over 16 LIGHT bytes under a mask.  m8 is the
+// mask byte repeated eight times; masked bytes are compared, so with m8 == 0 every bit is set.
+MM_DEV uint64_t mask_bytes8(uint32_t m) { return (uint64_t)(m & 0xffu) * 0x0101010101010101ull; }
+
+// bit i = byte i of a == byte i of b under the mask, i = 0..15
+MM_DEV uint32_t eq_bytes16_masked(const uint4& a, const uint4& b, uint64_t m8)
+{
+    return eq_bytes(u64_of(a.x, a.y) & m8, u64_of(b.x, b.y) & m8) | (eq_bytes(u64_of(a.z, a.w) & m8, u64_of(b.z, b.w) & m8) << 8);
+}
+
+// bit i = byte i of a == byte i - 1 of a under the mask; byte 0 is compared with `below`
+MM_DEV uint32_t eq_bytes16_below_masked(const uint4& a, uint32_t below, uint64_t m8)
+{
+    const uint64_t lo = u64_of(a.x, a.y) & m8, hi = u64_of(a.z, a.w) & m8;
+    return eq_bytes(lo, (lo << 8) | ((uint64_t)below & m8 & 0xffull)) | (eq_bytes(hi, (hi << 8) | (lo >> 56)) << 8);
+}
+
 MM_DEV uint32_t wave_incl_scan(uint32_t v, int lane)
 {
 #pragma unroll

@@ -347,6 +347,50 @@ class MMGen:
             return dict(quads=quads, section_quads=secq, chunk_quads=chq, quad_offset=off, total=int(tot.item()))
         return dict(quads=quads[:total], section_quads=secq, chunk_quads=chq, quad_offset=off, total=total)
 
+    def mesh_lit_section_quads(self, blocks, light, nx=None, nz=None, neighbor_idx=None, chunk_idx=None, capacity_quads=None, light_mask=0xff):
+        """mesh_section_quads with flat per-face light (include/mmgen.h "lit section quad mesh"): light uint8 [slots, 98304] indexed like blocks
+        (the output of light()); two faces share a quad only if they share the block id and the light of the voxel in front of them under
+        light_mask.  Returns the dict of mesh_section_quads plus quad_light uint8 [Q or capacity], the face light of every record (the capped
+        form pre-fills it with 0xf9); section_draws accepts the dict as it is."""
+        t = self.torch
+        n = blocks.shape[0] if chunk_idx is None else chunk_idx.shape[0]
+        vp, i32, u64, u8 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint8
+        self.lib.mmgen_mesh_lit_section_quads_count.argtypes = [vp, vp, vp, vp, i32, u8, vp, vp, vp]
+        self.lib.mmgen_mesh_lit_section_quads_fill.argtypes = [vp, vp, vp, vp, i32, u8, vp, vp, u64, vp, vp, vp]
+        self.lib.mmgen_mesh_offsets.argtypes = [vp, i32, vp, vp, vp]
+        assert light.dtype == t.uint8 and light.shape == blocks.shape and light.is_contiguous() and 0 <= int(light_mask) <= 0xff
+        if neighbor_idx is None and nx is not None:
+            assert chunk_idx is None, "a grid shape names the neighbours of chunks 0 .. n-1; give neighbor_idx with chunk_idx"
+            c = t.arange(n, dtype=t.int32, device=blocks.device)
+            x, z = c % nx, c // nx
+            neg = t.full_like(c, -1)
+            neighbor_idx = t.stack([t.where(z < nz - 1, c + nx, neg), t.where(x < nx - 1, c + 1, neg), t.where(z > 0, c - nx, neg),
+                                    t.where(x > 0, c - 1, neg)], dim=1).contiguous()
+        secq = self._empty((max(n, 1), self.SECTIONS), t.int32)[:n]
+        chq = self._empty((n,), t.int32)
+        self._check(self.lib.mmgen_mesh_lit_section_quads_count(self._p(blocks), self._p(light), self._p(chunk_idx), self._p(neighbor_idx), n, int(light_mask),
+                                                                self._p(secq), self._p(chq), self._stream()), "mmgen_mesh_lit_section_quads_count")
+        if capacity_quads is None:
+            incl = t.cumsum(chq.to(t.int64), 0)
+            off = (incl - chq).contiguous()
+            total = int(incl[-1].item()) if n else 0
+            quads, ql = self._empty((max(total, 1),), t.int32), self._empty((max(total, 1),), t.uint8)
+            capacity = 2 ** 64 - 1
+        else:
+            off = self._empty((max(n, 1),), t.int64)[:n]
+            tot = self._empty((1,), t.int64)
+            quads = t.full((capacity_quads,), -7, dtype=t.int32, device=blocks.device)
+            ql = t.full((capacity_quads,), 0xf9, dtype=t.uint8, device=blocks.device)
+            self._check(self.lib.mmgen_mesh_offsets(self._p(chq), n, self._p(off), self._p(tot), self._stream()), "mmgen_mesh_offsets")
+            total, capacity = None, capacity_quads
+        if n:
+            self._check(self.lib.mmgen_mesh_lit_section_quads_fill(self._p(blocks), self._p(light), self._p(chunk_idx), self._p(neighbor_idx), n, int(light_mask),
+                                                                   self._p(secq), self._p(off), capacity, self._p(quads), self._p(ql), self._stream()),
+                        "mmgen_mesh_lit_section_quads_fill")
+        if total is None:
+            return dict(quads=quads, quad_light=ql, section_quads=secq, chunk_quads=chq, quad_offset=off, total=int(tot.item()))
+        return dict(quads=quads[:total], quad_light=ql[:total], section_quads=secq, chunk_quads=chq, quad_offset=off, total=total)
+
     @classmethod
     def section_quad_fields(cls, quads):
         """Decodes section quad records (int32 tensor or array) into a dict of numpy fields x, y (0..15, local to the section), z, kind,

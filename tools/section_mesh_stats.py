@@ -2,7 +2,9 @@
 """Size and time of the section-bucketed quad mesh beside the chunk-wide greedy stream (section 6.6) on the 32 x 32-chunk
 region that tools/quad_mesh_stats.py and tools/visibility_stats.py use, all in one process: records and bytes per chunk of both streams, count +
 fill of both meshers, k_section_draws beside k_visible_sections, and for the three eyes of tools/visibility_stats.py the quads that the draw list
-really draws beside the quads of the 64-bit stream whose ORIGIN lies in a visible section (not conservative: section 6.8).  Times are the
+really draws beside the quads of the 64-bit stream whose ORIGIN lies in a visible section (not conservative: section 6.8); and the lit section
+stream (section 6.10) on the region lit by mmgen_light: records at four light masks against the unlit stream, bytes per chunk with the light
+bytes against mesh + resident light volume, count + fill twice in alternation with the unlit section mesher.  Times are the
 library's own per-kernel profile over the whole region, after a warm-up, median / min / max over the repeats.  MMGEN_LIB selects an A/B build.
 
 usage: tools/section_mesh_stats.py [--cx 1488 --cz -1110 --nx 32 --nz 32 --warmup 5 --reps 30]"""
@@ -44,6 +46,17 @@ def main():
           f"{4.0 * sq.sum() / (8.0 * gq.sum()):.3f}; {area.mean():.2f} unit faces per section quad; {np.count_nonzero(secq)} of {24 * n} sections have records, "
           f"largest section {secq.max()}")
 
+    # the lit section stream: how much light-aware merging splits this terrain
+    light = gen.light(gen.light_masks(blocks), grid)
+    for mask in (0xFF, 0xF0, 0xCC, 0x00):
+        lit = gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz, light_mask=mask)
+        lq = lit["chunk_quads"].cpu().numpy()
+        same = mask != 0 or (t.equal(lit["quads"], sec["quads"]) and not bool(lit["quad_light"].any()))
+        print(f"lit section stream, light_mask 0x{mask:02X}: {lit['total']} records = x {lit['total'] / max(sec['total'], 1):.4f} of the unlit {sec['total']}; "
+              f"{lq.mean():.1f} per chunk (max {lq.max()}) = {5.0 * lq.mean():.0f} bytes with the light bytes, against {4.0 * sq.mean():.0f} + 98304 = "
+              f"{4.0 * sq.mean() + 98304:.0f} for mesh + light volume (x {5.0 * lq.mean() / (4.0 * sq.mean() + 98304):.4f})"
+              + ("" if mask else f"; equals the unlit stream: {same}"))
+
     # the eyes of tools/visibility_stats.py: the middle column of the middle chunk, two voxels above its ground; its lowest see-through voxel; above the world
     ecx, ecz = a.nx // 2, a.nz // 2
     radius = max(ecx, a.nx - 1 - ecx, ecz, a.nz - 1 - ecz)
@@ -75,10 +88,18 @@ def main():
                               ("  its count", lambda: gen.mesh_quads(blocks, a.nx, a.nz), ("k_quads_count",)),
                               ("section mesher", lambda: gen.mesh_section_quads(blocks, a.nx, a.nz), ("k_section_quads_count", "k_section_quads_fill")),
                               ("greedy mesher", lambda: gen.mesh_quads(blocks, a.nx, a.nz), ("k_quads_count", "k_quads_fill")),
+                              ("lit section mesher", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz), ("k_lit_section_quads_count", "k_lit_section_quads_fill")),
+                              ("  its count", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz), ("k_lit_section_quads_count",)),
+                              ("section mesher", lambda: gen.mesh_section_quads(blocks, a.nx, a.nz), ("k_section_quads_count", "k_section_quads_fill")),
+                              ("lit section mesher", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz), ("k_lit_section_quads_count", "k_lit_section_quads_fill")),
+                              ("section mesher", lambda: gen.mesh_section_quads(blocks, a.nx, a.nz), ("k_section_quads_count", "k_section_quads_fill")),
+                              # A/B: at light_mask 0 the lit kernels emit the unlit records, so what is left over the unlit mesher is the six staged passes
+                              ("lit, mask 0x00", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz, light_mask=0), ("k_lit_section_quads_count", "k_lit_section_quads_fill")),
+                              ("  its count", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz, light_mask=0), ("k_lit_section_quads_count",)),
                               ("draw list", lambda: gen.section_draws(vis, grid, (ecx, ecz), radius, sec), ("k_section_draws",)),
                               ("visible set", lambda: gen.visible_sections(conn, grid, (ecx, eyes[0][1], ecz), radius), ("k_visible_sections",))):
         med, lo, hi = kernel_ms(gen, fn, kernels, a.warmup, a.reps)
-        print(f"{name:14s} median {med:.3f} ms (min {lo:.3f}, max {hi:.3f}) over {a.reps} runs = {1e3 * med / n:.2f} us per chunk")
+        print(f"{name:18s} median {med:.3f} ms (min {lo:.3f}, max {hi:.3f}) over {a.reps} runs = {1e3 * med / n:.2f} us per chunk")
 
 
 if __name__ == "__main__":
