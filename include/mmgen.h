@@ -531,6 +531,46 @@ int mmgen_mesh_lit_section_quads_fill(const uint8_t* d_blocks, const uint8_t* d_
                                       uint8_t light_mask, const uint32_t* d_section_quads, const uint64_t* d_quad_offset, uint64_t capacity_quads,
                                       uint32_t* d_quads, uint8_t* d_quad_light, void* stream);
 
+/* ---- section quad mesh with ambient occlusion: per-corner AO in the greedy key ----------------------------------------------
+ * The lit section stream with the shading a voxel world is expected to have: every face carries the darkening of its four corners by the
+ * opaque blocks that touch them, two faces share a quad only if they share the block id, the face light AND the four corner values, and every
+ * record has its AO byte (mmgen_types.h "face AO byte") in a second parallel byte stream.
+ * d_blocks / d_light / d_chunk_idx / light_mask exactly as in mmgen_mesh_lit_section_quads_*, but d_light may be NULL iff light_mask == 0: then
+ * every light byte is 0 and the light volume is not read.
+ * d_neighbor_idx8 [n][8]: entries 0..3 = N (+z), E (+x), S (-z), W (-x) as in d_neighbor_idx; entries 4..7 = the diagonals (+x,+z), (+x,-z),
+ * (-x,-z), (-x,+z); -1 = absent, NULL = all absent.
+ *
+ * UNCHANGED: the face set F is that of mmgen_mesh_section_quads_*, word for word, and uses entries 0..3 only; directions, sections, planes,
+ * the face light FL, the record format, the ORDER, the section ranges, count -> mmgen_mesh_offsets -> fill and "a section never writes more
+ * records than were counted for it" are those of mmgen_mesh_lit_section_quads_*.
+ * OCCLUDER: O(u) = 1 iff u lies in the chunk or in one of its eight PRESENT neighbour chunks, 0 <= u.y <= 383, and the class of u is OPAQUE
+ * (ids >= MMB_NUM_BLOCKS count as OPAQUE).  Everything else - absent chunks, voxels beyond the 18 x 18 column halo, below or above the world -
+ * does not occlude.
+ * FACE AO: for a face (v, d) of F let f = v + dirVec(d) and e_r, e_q the unit steps of the plane's row axis and fast axis (d in {0, 2}: r = x,
+ * q = y;  d in {1, 3}: r = z, q = y;  d in {4, 5}: r = z, q = x).  Corner k = 2 [r side is +] + [q side is +], k = 0..3, has the signs (s_r, s_q):
+ *     s1 = O(f + s_r e_r),  s2 = O(f + s_q e_q),  c = O(f + s_r e_r + s_q e_q);   ao_k = 0 if s1 and s2, else 3 - (s1 + s2 + c);
+ *     AO(v, d) = sum of ao_k << 2k.   An unoccluded face has MMGEN_AO_NONE = 0xFF.
+ *   A kind-6 record (X-shaped block) has AO 0xFF and its own voxel's light.
+ * GREEDY RULE: that of mmgen_mesh_section_quads_* with "of id b" replaced by "of id b, of face light FL(r0, q0) and of face AO AO(r0, q0)",
+ * for L and for W alike.  Nothing merges across a section border or a chunk border.
+ * FOR THE CONSUMER: the four corner values are interpolated bilinearly inside each CELL of the quad, by the fractional part of the tiled
+ * coordinate that already tiles the block's texture; every cell of a quad has the same AO byte, so the merged quad shades exactly like its
+ * unmerged faces.
+ * The stream of a chunk is a pure function of its blocks and light, its eight neighbours' blocks, its four side neighbours' light, which
+ * neighbours are present, and light_mask.
+ *
+ *   mmgen_mesh_ao_section_quads_count: d_section_quads [n][24] and d_chunk_quads [n] receive the record counts.
+ *   mmgen_mesh_ao_section_quads_fill : d_quads, d_quad_light as in mmgen_mesh_lit_section_quads_fill; d_quad_ao[k] is the AO byte of record k.
+ *                           A chunk whose records would end beyond capacity_quads writes NONE of the three arrays; UINT64_MAX = uncapped.
+ *                           Blocks, light, neighbours and light_mask must be those of the count.
+ * n == 0 succeeds without a launch; capacity_quads == 0, null pointers (d_light under the rule above) and n < 0 are hipErrorInvalidValue.
+ * Nothing is allocated; both calls are asynchronous on `stream`. */
+int mmgen_mesh_ao_section_quads_count(const uint8_t* d_blocks, const uint8_t* d_light, const int32_t* d_chunk_idx, const int32_t* d_neighbor_idx8, int n,
+                                      uint8_t light_mask, uint32_t* d_section_quads /*[n][24]*/, uint32_t* d_chunk_quads /*[n]*/, void* stream);
+int mmgen_mesh_ao_section_quads_fill(const uint8_t* d_blocks, const uint8_t* d_light, const int32_t* d_chunk_idx, const int32_t* d_neighbor_idx8, int n,
+                                     uint8_t light_mask, const uint32_t* d_section_quads, const uint64_t* d_quad_offset, uint64_t capacity_quads,
+                                     uint32_t* d_quads, uint8_t* d_quad_light, uint8_t* d_quad_ao, void* stream);
+
 /* ---- region wire format (the reference has none) ---------------------------------------------
  * A chunk's 98 304 block ids as per-column run-length pairs: u16 runsOfColumn[256], then for each column (x + 16 z, the blocks[]
  * order) its runs as (u8 blockId, u8 length - 1), 1 .. 256 voxels per pair.  512 + 2 R bytes per chunk (typically 5 - 9 KB).

@@ -122,6 +122,10 @@ typedef struct mmgen_camera {                /* pinhole camera in the rays' coor
  * Rows and fast axis per direction: d in {0, 2}: r = x, q = y;  d in {1, 3}: r = z, q = y;  d in {4, 5}: r = z, q = x.  A kind-6 record has
  * W - 1 = L - 1 = 0.  The section (chunk, sy) is not in the record: it follows from the record's position (mmgen_section_draw.origin). */
 #define MMGEN_SECTIONS_PER_CHUNK 24
+/* ---- face AO byte (mmgen.h "section quad mesh with ambient occlusion"): one uint8_t per record, parallel to the records ----
+ *   bits 2k, 2k+1 = ao of corner k = 2 [row side is +] + [fast-axis side is +] of every cell of the quad (rows r and fast axis q as above):
+ *   3 = open, 2 / 1 = one / two of {side, side, corner} opaque, 0 = both sides opaque.  0xFF = unoccluded; every kind-6 record has 0xFF. */
+#define MMGEN_AO_NONE 0xFFu
 /* one contiguous range of section quad records = one section that has to be drawn (mmgen_section_draws) */
 typedef struct mmgen_section_draw {          /* 16 bytes */
     uint64_t first;                          /* index of the section's first record in d_quads */

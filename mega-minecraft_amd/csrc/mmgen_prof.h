@@ -18,6 +18,7 @@ enum KernelId {
     KID_LIGHT_MASKS, KID_LIGHT, KID_SECTION_CONN, KID_VISIBLE_SECTIONS,
     KID_SECTION_QUADS_COUNT, KID_SECTION_QUADS_FILL, KID_SECTION_DRAWS,
     KID_LIT_SECTION_QUADS_COUNT, KID_LIT_SECTION_QUADS_FILL,
+    KID_AO_SECTION_QUADS_COUNT, KID_AO_SECTION_QUADS_FILL,
     KID_COUNT
 };
 

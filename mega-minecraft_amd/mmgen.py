@@ -391,6 +391,54 @@ class MMGen:
             return dict(quads=quads, quad_light=ql, section_quads=secq, chunk_quads=chq, quad_offset=off, total=int(tot.item()))
         return dict(quads=quads[:total], quad_light=ql[:total], section_quads=secq, chunk_quads=chq, quad_offset=off, total=total)
 
+    def mesh_ao_section_quads(self, blocks, light, nx=None, nz=None, neighbor_idx8=None, chunk_idx=None, capacity_quads=None, light_mask=0xff):
+        """mesh_lit_section_quads with per-corner ambient occlusion (include/mmgen.h "section quad mesh with ambient occlusion"): two faces share a
+        quad only if they also share the AO byte of mmgen_types.h.  neighbor_idx8 int32 [n, 8]: N E S W, then the diagonals (+x,+z) (+x,-z)
+        (-x,-z) (-x,+z), -1 = absent; a grid shape builds all eight.  light may be None iff light_mask == 0.  Returns the dict of
+        mesh_lit_section_quads plus quad_ao uint8 [Q or capacity] (the capped form pre-fills it with 0xf9); section_draws accepts the dict as it is."""
+        t = self.torch
+        n = blocks.shape[0] if chunk_idx is None else chunk_idx.shape[0]
+        vp, i32, u64, u8 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint8
+        self.lib.mmgen_mesh_ao_section_quads_count.argtypes = [vp, vp, vp, vp, i32, u8, vp, vp, vp]
+        self.lib.mmgen_mesh_ao_section_quads_fill.argtypes = [vp, vp, vp, vp, i32, u8, vp, vp, u64, vp, vp, vp, vp]
+        self.lib.mmgen_mesh_offsets.argtypes = [vp, i32, vp, vp, vp]
+        assert 0 <= int(light_mask) <= 0xff and (light is not None or int(light_mask) == 0)
+        assert light is None or (light.dtype == t.uint8 and light.shape == blocks.shape and light.is_contiguous())
+        if neighbor_idx8 is None and nx is not None:
+            assert chunk_idx is None, "a grid shape names the neighbours of chunks 0 .. n-1; give neighbor_idx8 with chunk_idx"
+            c = t.arange(n, dtype=t.int32, device=blocks.device)
+            x, z = c % nx, c // nx
+            neg = t.full_like(c, -1)
+            n_, e_, s_, w_ = z < nz - 1, x < nx - 1, z > 0, x > 0
+            neighbor_idx8 = t.stack([t.where(n_, c + nx, neg), t.where(e_, c + 1, neg), t.where(s_, c - nx, neg), t.where(w_, c - 1, neg),
+                                     t.where(e_ & n_, c + nx + 1, neg), t.where(e_ & s_, c - nx + 1, neg), t.where(w_ & s_, c - nx - 1, neg),
+                                     t.where(w_ & n_, c + nx - 1, neg)], dim=1).contiguous()
+        assert neighbor_idx8 is None or (neighbor_idx8.dtype == t.int32 and tuple(neighbor_idx8.shape) == (n, 8) and neighbor_idx8.is_contiguous())
+        secq = self._empty((max(n, 1), self.SECTIONS), t.int32)[:n]
+        chq = self._empty((n,), t.int32)
+        self._check(self.lib.mmgen_mesh_ao_section_quads_count(self._p(blocks), self._p(light), self._p(chunk_idx), self._p(neighbor_idx8), n, int(light_mask),
+                                                               self._p(secq), self._p(chq), self._stream()), "mmgen_mesh_ao_section_quads_count")
+        if capacity_quads is None:
+            incl = t.cumsum(chq.to(t.int64), 0)
+            off = (incl - chq).contiguous()
+            total = int(incl[-1].item()) if n else 0
+            quads, ql, qa = self._empty((max(total, 1),), t.int32), self._empty((max(total, 1),), t.uint8), self._empty((max(total, 1),), t.uint8)
+            capacity = 2 ** 64 - 1
+        else:
+            off = self._empty((max(n, 1),), t.int64)[:n]
+            tot = self._empty((1,), t.int64)
+            quads = t.full((capacity_quads,), -7, dtype=t.int32, device=blocks.device)
+            ql, qa = (t.full((capacity_quads,), 0xf9, dtype=t.uint8, device=blocks.device) for _ in range(2))
+            self._check(self.lib.mmgen_mesh_offsets(self._p(chq), n, self._p(off), self._p(tot), self._stream()), "mmgen_mesh_offsets")
+            total, capacity = None, capacity_quads
+        if n:
+            self._check(self.lib.mmgen_mesh_ao_section_quads_fill(self._p(blocks), self._p(light), self._p(chunk_idx), self._p(neighbor_idx8), n, int(light_mask),
+                                                                  self._p(secq), self._p(off), capacity, self._p(quads), self._p(ql), self._p(qa), self._stream()),
+                        "mmgen_mesh_ao_section_quads_fill")
+        if total is None:
+            return dict(quads=quads, quad_light=ql, quad_ao=qa, section_quads=secq, chunk_quads=chq, quad_offset=off, total=int(tot.item()))
+        return dict(quads=quads[:total], quad_light=ql[:total], quad_ao=qa[:total], section_quads=secq, chunk_quads=chq, quad_offset=off, total=total)
+
     @classmethod
     def section_quad_fields(cls, quads):
         """Decodes section quad records (int32 tensor or array) into a dict of numpy fields x, y (0..15, local to the section), z, kind,

@@ -4,7 +4,9 @@ region that tools/quad_mesh_stats.py and tools/visibility_stats.py use, all in o
 fill of both meshers, k_section_draws beside k_visible_sections, and for the three eyes of tools/visibility_stats.py the quads that the draw list
 really draws beside the quads of the 64-bit stream whose ORIGIN lies in a visible section (not conservative: section 6.8); and the lit section
 stream (section 6.10) on the region lit by mmgen_light: records at four light masks against the unlit stream, bytes per chunk with the light
-bytes against mesh + resident light volume, count + fill twice in alternation with the unlit section mesher.  Times are the
+bytes against mesh + resident light volume, count + fill twice in alternation with the unlit section mesher; and the AO section stream
+(section 6.11): records at three light masks against the lit and the unlit stream, count + fill twice in alternation with the lit mesher, and
+both on a flat world where nothing occludes and the two emit the same records.  Times are the
 library's own per-kernel profile over the whole region, after a warm-up, median / min / max over the repeats.  MMGEN_LIB selects an A/B build.
 
 usage: tools/section_mesh_stats.py [--cx 1488 --cz -1110 --nx 32 --nz 32 --warmup 5 --reps 30]"""
@@ -57,6 +59,22 @@ def main():
               f"{4.0 * sq.mean() + 98304:.0f} for mesh + light volume (x {5.0 * lq.mean() / (4.0 * sq.mean() + 98304):.4f})"
               + ("" if mask else f"; equals the unlit stream: {same}"))
 
+    # the AO section stream: what corner occlusion splits on top of the light
+    for mask in (0xFF, 0xF0, 0x00):
+        ao = gen.mesh_ao_section_quads(blocks, light if mask else None, a.nx, a.nz, light_mask=mask)
+        lit = gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz, light_mask=mask)
+        aq = ao["chunk_quads"].cpu().numpy()
+        print(f"AO section stream, light_mask 0x{mask:02X}: {ao['total']} records = x {ao['total'] / max(lit['total'], 1):.4f} of the lit {lit['total']}, x "
+              f"{ao['total'] / max(sec['total'], 1):.4f} of the unlit {sec['total']}; {aq.mean():.1f} per chunk (max {aq.max()}) = {6.0 * aq.mean():.0f} bytes with "
+              f"light and AO bytes; {100.0 * float((ao['quad_ao'] == 0xFF).float().mean()):.1f} % of the records unoccluded")
+    flat = t.zeros_like(blocks).reshape(n, 256, 384)
+    flat[:, :, :64] = 57
+    flat = flat.reshape(n, -1)
+    fl = gen.light(gen.light_masks(flat), grid)
+    fa, fb = gen.mesh_ao_section_quads(flat, fl, a.nx, a.nz), gen.mesh_lit_section_quads(flat, fl, a.nx, a.nz)
+    print(f"flat world (rock below y = 64): AO stream {fa['total']} records, lit stream {fb['total']}; equal records and light: "
+          f"{t.equal(fa['quads'], fb['quads']) and t.equal(fa['quad_light'], fb['quad_light'])}; all unoccluded: {bool((fa['quad_ao'] == 0xFF).all())}")
+
     # the eyes of tools/visibility_stats.py: the middle column of the middle chunk, two voxels above its ground; its lowest see-through voxel; above the world
     ecx, ecz = a.nx // 2, a.nz // 2
     radius = max(ecx, a.nx - 1 - ecx, ecz, a.nz - 1 - ecz)
@@ -96,6 +114,15 @@ def main():
                               # A/B: at light_mask 0 the lit kernels emit the unlit records, so what is left over the unlit mesher is the six staged passes
                               ("lit, mask 0x00", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz, light_mask=0), ("k_lit_section_quads_count", "k_lit_section_quads_fill")),
                               ("  its count", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz, light_mask=0), ("k_lit_section_quads_count",)),
+                              ("AO section mesher", lambda: gen.mesh_ao_section_quads(blocks, light, a.nx, a.nz), ("k_ao_section_quads_count", "k_ao_section_quads_fill")),
+                              ("  its count", lambda: gen.mesh_ao_section_quads(blocks, light, a.nx, a.nz), ("k_ao_section_quads_count",)),
+                              ("lit section mesher", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz), ("k_lit_section_quads_count", "k_lit_section_quads_fill")),
+                              ("AO section mesher", lambda: gen.mesh_ao_section_quads(blocks, light, a.nx, a.nz), ("k_ao_section_quads_count", "k_ao_section_quads_fill")),
+                              ("lit section mesher", lambda: gen.mesh_lit_section_quads(blocks, light, a.nx, a.nz), ("k_lit_section_quads_count", "k_lit_section_quads_fill")),
+                              ("AO, mask 0x00", lambda: gen.mesh_ao_section_quads(blocks, None, a.nx, a.nz, light_mask=0), ("k_ao_section_quads_count", "k_ao_section_quads_fill")),
+                              # A/B: on the flat world nothing occludes and both emit the same records: what is left is the structure (halo, AO equality, AO bytes)
+                              ("AO, flat world", lambda: gen.mesh_ao_section_quads(flat, fl, a.nx, a.nz), ("k_ao_section_quads_count", "k_ao_section_quads_fill")),
+                              ("lit, flat world", lambda: gen.mesh_lit_section_quads(flat, fl, a.nx, a.nz), ("k_lit_section_quads_count", "k_lit_section_quads_fill")),
                               ("draw list", lambda: gen.section_draws(vis, grid, (ecx, ecz), radius, sec), ("k_section_draws",)),
                               ("visible set", lambda: gen.visible_sections(conn, grid, (ecx, eyes[0][1], ecz), radius), ("k_visible_sections",))):
         med, lo, hi = kernel_ms(gen, fn, kernels, a.warmup, a.reps)
