@@ -571,6 +571,32 @@ int mmgen_mesh_ao_section_quads_fill(const uint8_t* d_blocks, const uint8_t* d_l
                                      uint8_t light_mask, const uint32_t* d_section_quads, const uint64_t* d_quad_offset, uint64_t capacity_quads,
                                      uint32_t* d_quads, uint8_t* d_quad_light, uint8_t* d_quad_ao, void* stream);
 
+/* ---- level-of-detail chunks: s x s source chunks reduced to one chunk-shaped volume of s^3-block cells ------------------------
+ * The far field for every consumer above: the output is a chunk slot in the standard layout, AIR above its content, so a grid of level-k
+ * slots is lit, culled, meshed and ray cast by the calls of this header unchanged; the consumer multiplies positions by s.  The reference
+ * has nothing like it.
+ *
+ * THE CONTRACT (mmgen_lod_reduce)
+ *   level is 1, 2 or 3 and s = 1 << level.  LOD chunk i covers the s x s source chunks d_src_idx[i][qx + s qz], qx, qz in 0..s-1 along +x and
+ *   +z: slots of d_blocks, -1 = absent (reads as all AIR); a slot may appear in several lists.  LOD chunk i is written to slot d_dst_idx[i]
+ *   of d_lod_blocks (slot i when NULL): all 98 304 bytes, index Y + 384 (X + 16 Z); every other slot stays untouched.  d_lod_blocks must not
+ *   overlap a source slot that is read, and the destination slots must be distinct.
+ *   Coarse voxel (X, Y, Z), X, Z in 0..15, Y in 0..384/s - 1, has the cube C of the s^3 source voxels at footprint columns (s X + i, s Z + j)
+ *   and y in [s Y, s Y + s); footprint column gx belongs to source chunk qx = gx >> 4 at local x = gx & 15, and so for z.  Y >= 384/s is AIR.
+ *   Classes are the mesher's; ids >= MMB_NUM_BLOCKS are OPAQUE.  A voxel is CONTENT iff its class is OPAQUE, SEMI or TRANSPARENT: AIR and
+ *   X_SHAPED are not, so flowers and grass tufts vanish with distance.
+ *   SOLIDITY: with N the number of content voxels of C, the cell is AIR (0) iff 2 N < s^3: the surface is rounded to the nearest cell, and
+ *   exactly half counts as solid.
+ *   BLOCK ID of a solid cell: every column of C that holds a content voxel gives one sample.  y1 is its highest content voxel inside C, y2
+ *   the largest y with y1 <= y2 <= min(s Y + 2 s - 1, 383) such that every voxel y1..y2 of that source column is content; the sample is the
+ *   id at y2.  (The look-ahead of at most s voxels into the cube above keeps a grass or water skin on a cell whose own top voxel is dirt.)
+ *   The cell's id is the id with the most samples, ties to the lowest id.
+ *   The output is a pure function of the listed source chunks and level.  It is NOT a cascade: level k is defined from level 0.
+ *   Null d_blocks, d_src_idx or d_lod_blocks, n < 0 and a level outside [1, 3] are hipErrorInvalidValue; n == 0 succeeds without a launch.
+ * Nothing is allocated; the call is asynchronous on `stream`. */
+int mmgen_lod_reduce(const uint8_t* d_blocks, const int32_t* d_src_idx /*[n][s*s]*/, int n, int level,
+                     uint8_t* d_lod_blocks /*[*][98304]*/, const int32_t* d_dst_idx /*[n], NULL = 0..n-1*/, void* stream);
+
 /* ---- region wire format (the reference has none) ---------------------------------------------
  * A chunk's 98 304 block ids as per-column run-length pairs: u16 runsOfColumn[256], then for each column (x + 16 z, the blocks[]
  * order) its runs as (u8 blockId, u8 length - 1), 1 .. 256 voxels per pair.  512 + 2 R bytes per chunk (typically 5 - 9 KB).

@@ -19,6 +19,7 @@ enum KernelId {
     KID_SECTION_QUADS_COUNT, KID_SECTION_QUADS_FILL, KID_SECTION_DRAWS,
     KID_LIT_SECTION_QUADS_COUNT, KID_LIT_SECTION_QUADS_FILL,
     KID_AO_SECTION_QUADS_COUNT, KID_AO_SECTION_QUADS_FILL,
+    KID_LOD_REDUCE,
     KID_COUNT
 };
 

@@ -25,7 +25,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_light_masks", "k_light", "k_section_conn", "k_visible_sections",
     "k_section_quads_count", "k_section_quads_fill", "k_section_draws",
     "k_lit_section_quads_count", "k_lit_section_quads_fill",
-    "k_ao_section_quads_count", "k_ao_section_quads_fill"};
+    "k_ao_section_quads_count", "k_ao_section_quads_fill",
+    "k_lod_reduce"};
 
 hipEvent_t get_event()
 {

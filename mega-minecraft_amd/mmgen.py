@@ -639,6 +639,22 @@ class MMGen:
                                                     self._stream()), "mmgen_visible_sections")
         return vis
 
+    # ------------------------------------------------------------------ level-of-detail chunks (include/mmgen.h)
+    def lod_reduce(self, blocks, src_idx, level, out=None, dst_idx=None):
+        """src_idx: int32 [n, s * s] device tensor, s = 1 << level (1..3): the slots of `blocks` (uint8 [slots, 98304]) under LOD chunk i in
+        the order qx + s qz, -1 = absent.  LOD chunk i goes to slot dst_idx[i] of `out` (int32 [n] device tensor, None = slot i); `out` is
+        allocated as uint8 [n, 98304] when None and must not share memory with `blocks`.  Returns the output tensor."""
+        t = self.torch
+        vp, i32 = ctypes.c_void_p, ctypes.c_int
+        self.lib.mmgen_lod_reduce.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+        assert src_idx.dtype == t.int32 and src_idx.dim() == 2 and src_idx.is_contiguous() and src_idx.shape[1] == 1 << (2 * int(level))
+        assert dst_idx is None or (dst_idx.dtype == t.int32 and dst_idx.numel() == src_idx.shape[0] and dst_idx.is_contiguous())
+        n = src_idx.shape[0]
+        lod = out if out is not None else self._empty((n, BLOCKS), t.uint8)
+        self._check(self.lib.mmgen_lod_reduce(self._p(blocks), self._p(src_idx), n, int(level), self._p(lod), self._p(dst_idx), self._stream()),
+                    "mmgen_lod_reduce")
+        return lod
+
     # ------------------------------------------------------------------ region fast path (all stages, device resident)
     EROSION, FEATURES, DECORATORS = 1, 2, 4
 
