@@ -354,6 +354,52 @@ int mmgen_raycast(const uint8_t* d_blocks, const int32_t* d_grid, int grid_w, in
 int mmgen_raycast_camera(const uint8_t* d_blocks, const int32_t* d_grid, int grid_w, int grid_h, const uint8_t* d_occupancy, unsigned stop_mask, unsigned flags,
                          const mmgen_camera* cam, float t_max, mmgen_ray_hit* d_hits, void* stream);
 
+/* ---- shaded camera render: camera -> RGBA8 in one launch (light, AO, water, sun shadow, fog) ---------------------------------
+ * The reference's product is an image.  mmgen_render_camera turns what this header keeps on the device - blocks, the light volume, the
+ * occluder rule of the AO mesher - into pixels without a host round trip.  d_blocks, d_grid, cam and the pixel-to-ray formula are exactly
+ * those of mmgen_raycast_camera; d_rgba [height][width] = r | g << 8 | b << 16 | alpha << 24.  The image is a pure function of the inputs.
+ *
+ * WALKS, all three THE TRAVERSAL CONTRACT above, unchanged, with p->t_max:
+ *   A  the pixel's camera ray, stop_mask = p->first_mask (must contain MMGEN_RAY_OPAQUE), occupancy d_occ_first.  d_hits, when given,
+ *      receives exactly what mmgen_raycast_camera writes for that mask.
+ *   B  only with MMGEN_RENDER_TRANSLUCENT when A is a HIT on a TRANSPARENT-class block: the same ray (o, d), stop_mask = OPAQUE | SEMI,
+ *      occupancy d_occ_second; its result is that of a fresh walk.
+ *   S  only with MMGEN_RENDER_SUN_SHADOW when A is a HIT with face != 6: o = the centre of the front voxel f = v + dirVec(face)
+ *      (f_a + 0.5f, exact in f32), d = p->sun_dir, stop_mask = OPAQUE | SEMI, occupancy d_occ_second.  The pixel is SHADOWED iff S is a HIT
+ *      (an INVALID S does not shadow).
+ *   d_occ_second may be NULL iff neither of the two flags is set.
+ * SHADING is integer only.  mul8(a, b) = (a * b + 127) / 255.
+ *     RAMP[0..15] = 9, 11, 14, 18, 22, 27, 34, 43, 53, 67, 84, 104, 131, 163, 204, 255
+ *     FACE[0..6]  = 204, 179, 153, 179, 255, 115, 255          AOW[0..3] = 115, 153, 204, 255
+ *   shade(hit) for a HIT with voxel v, face, block id:  f = v + dirVec(face) (f = v when face == 6);  L = d_light at f when 0 <= f.y <= 383
+ *   (indexed like d_blocks through d_grid; the walk guarantees that f's chunk is present), 0xF0 above the world, 0x00 below it, 0xF0
+ *   everywhere when d_light is NULL;  lv = max((L >> 4) * sun_level / 15, L & 15);  per channel c of palette[id]:
+ *   x = mul8(mul8(c, RAMP[lv]), FACE[face]).
+ *   Walk A's hit takes two more factors: with MMGEN_RENDER_AO, face != 6 and a block of class OPAQUE or SEMI, x = mul8(x, A); if the pixel
+ *   is shadowed, x = mul8(x, shadow_dim).
+ * AO FACTOR A: the occluder is that of the AO mesher taken over the whole grid: O(u) = 1 iff u lies in a present chunk, 0 <= u.y <= 383 and
+ *   its class is OPAQUE.  ao_k, k = 0..3, around f is the FACE AO formula below with its axes r and q.  The hit point on a tangential axis
+ *   a is h_a = o_a + t * d_a (one f32 multiply, one f32 add, not fused);  u_a = clamp((int)floorf((h_a - (float)v_a) * 16.0f), 0, 15);  the
+ *   weight of the + side of an axis is 2 u_a + 1, of the - side 31 - 2 u_a;  A = (sum over k of w_r(k) w_q(k) AOW[ao_k] + 512) >> 10.
+ * THE PIXEL
+ *   1  A is not a HIT: rgb = sky_rgb, alpha 0.          2  A is a HIT: C = shade(A) with its factors, alpha 255.
+ *   3  walk B was taken: back = shade(B) when B is a HIT (no AO, no shadow factor), else sky_rgb;
+ *      C = (C * al + back * (255 - al) + 127) / 255 per channel, al = the palette alpha of A's block.
+ *   4  MMGEN_RENDER_FOG and A is a HIT: g = (int)(fminf(fmaxf((t_A - fog_start) * (1.0f / (fog_end - fog_start)), 0.f), 1.f) * 255.0f + 0.5f),
+ *      every operation in f32;  C = (C * (255 - g) + sky_rgb * g + 127) / 255 per channel.
+ * d_palette [256] on the device, r | g << 8 | b << 16 | alpha << 24; NULL = the default table (mmgen_render_default_palette returns it: a
+ * colour per block id, alpha 255 except 150 for the TRANSPARENT-class ids).
+ * hipErrorInvalidValue: what mmgen_raycast_camera rejects; a first_mask without OPAQUE or above 15; unknown flag bits; sun_level > 15; with
+ * _FOG a fog_end that is not greater than fog_start or a fog value that is not finite; with _SUN_SHADOW a sun_dir that is zero or not
+ * finite; a NULL d_occ_second under the rule above; a NULL d_rgba, cam or p.  Nothing is allocated; the call is asynchronous on `stream`. */
+int mmgen_render_default_palette(uint32_t* h_out /*[256], host*/);
+int mmgen_render_camera(const uint8_t* d_blocks, const int32_t* d_grid, int grid_w, int grid_h,
+                        const uint8_t* d_occ_first, const uint8_t* d_occ_second /*nullable, see above*/,
+                        const uint8_t* d_light /*[*][98304], nullable = full bright (0xF0 everywhere)*/,
+                        const uint32_t* d_palette /*[256] device, NULL = default*/,
+                        const mmgen_camera* cam, const mmgen_render_params* p,
+                        uint32_t* d_rgba /*[height][width]*/, mmgen_ray_hit* d_hits /*[height][width], nullable*/, void* stream);
+
 /* ---- voxel lighting: sky and block light over device-resident chunks --------------------------------------------------------
  * The reference gets its illumination from an OptiX path tracer and an emissive texture.  Here every voxel gets the classic pair of
  * 4-bit values, each dropping by one per step through voxels that are not opaque.  d_blocks, d_grid [grid_h][grid_w] (index into the

@@ -97,6 +97,23 @@ typedef struct mmgen_camera {                /* pinhole camera in the rays' coor
     int32_t width, height;                   /* pixels */
 } mmgen_camera;
 
+/* ---- shaded camera render (mmgen_render_camera, include/mmgen.h) ---- */
+#define MMGEN_RENDER_AO 1u                   /* corner occlusion on walk A's hit */
+#define MMGEN_RENDER_TRANSLUCENT 2u          /* walk B behind a TRANSPARENT-class hit, blended by the palette alpha */
+#define MMGEN_RENDER_SUN_SHADOW 4u           /* walk S from the front voxel towards the sun */
+#define MMGEN_RENDER_FOG 8u                  /* blend towards sky_rgb by t */
+typedef struct mmgen_render_params {         /* 40 bytes */
+    uint32_t flags;                          /* MMGEN_RENDER_* */
+    uint32_t first_mask;                     /* stop_mask of walk A; must contain MMGEN_RAY_OPAQUE */
+    float t_max;                             /* of all three walks */
+    float sun_dir[3];                        /* points towards the sun; need not be normalised */
+    float fog_start, fog_end;                /* in t; fog_end > fog_start */
+    uint8_t sky_rgb[3];
+    uint8_t sun_level;                       /* 0..15: what sky light 15 is worth (15 = noon) */
+    uint8_t shadow_dim;                      /* mul8 factor of a shadowed pixel */
+    uint8_t pad[3];
+} mmgen_render_params;
+
 /* ---- voxel lighting (mmgen_light_masks / mmgen_light, include/mmgen.h) ----
  * The mask record of a chunk slot, c = x + 16 z, word w = y / 64, bit y % 64:
  *   u64 [256][6]     at     0   the voxel passes light (its class is not OPAQUE)

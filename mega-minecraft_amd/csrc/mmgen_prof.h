@@ -20,6 +20,7 @@ enum KernelId {
     KID_LIT_SECTION_QUADS_COUNT, KID_LIT_SECTION_QUADS_FILL,
     KID_AO_SECTION_QUADS_COUNT, KID_AO_SECTION_QUADS_FILL,
     KID_LOD_REDUCE,
+    KID_RENDER_CAMERA,
     KID_COUNT
 };
 

@@ -26,7 +26,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_section_quads_count", "k_section_quads_fill", "k_section_draws",
     "k_lit_section_quads_count", "k_lit_section_quads_fill",
     "k_ao_section_quads_count", "k_ao_section_quads_fill",
-    "k_lod_reduce"};
+    "k_lod_reduce",
+    "k_render_camera"};
 
 hipEvent_t get_event()
 {

@@ -558,6 +558,48 @@ class MMGen:
                                                   ctypes.byref(cam), t_max, self._p(hits), self._stream()), "mmgen_raycast_camera")
         return hits
 
+    # ------------------------------------------------------------------ shaded camera render (include/mmgen.h)
+    RENDER_AO, RENDER_TRANSLUCENT, RENDER_SUN_SHADOW, RENDER_FOG = 1, 2, 4, 8
+
+    def render_default_palette(self):
+        """The default palette (include/mmgen.h) as a numpy uint32 [256]: r | g << 8 | b << 16 | alpha << 24."""
+        import numpy as np
+        out = np.zeros(256, np.uint32)
+        self.lib.mmgen_render_default_palette.argtypes = [ctypes.c_void_p]
+        self._check(self.lib.mmgen_render_default_palette(out.ctypes.data), "mmgen_render_default_palette")
+        return out
+
+    def render_camera(self, blocks, grid, occ_first, eye, forward, up=(0.0, 1.0, 0.0), fov_y=1.0, width=640, height=360, occ_second=None, light=None,
+                      palette=None, flags=0, first_mask=15, t_max=4096.0, sun_dir=(0.45, 0.8, 0.3), fog_start=0.0, fog_end=4096.0,
+                      sky_rgb=(150, 190, 235), sun_level=15, shadow_dim=140, return_hits=False):
+        """One shaded pixel per camera ray (mmgen_render_camera) -> uint8 [height, width, 4] RGBA on the device, and with return_hits the
+        int32 [height, width, 5] records of walk A.  occ_first: ray_occupancy for first_mask; occ_second: ray_occupancy for stop mask 3
+        (OPAQUE | SEMI), needed with RENDER_TRANSLUCENT or RENDER_SUN_SHADOW; light: the volume of light(), None = full bright; palette:
+        uint32 [256] device tensor (int32 storage), None = the default."""
+        t = self.torch
+
+        class Camera(ctypes.Structure):
+            _fields_ = [("eye", ctypes.c_float * 3), ("forward", ctypes.c_float * 3), ("up", ctypes.c_float * 3), ("fov_y", ctypes.c_float),
+                        ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+        class Params(ctypes.Structure):
+            _fields_ = [("flags", ctypes.c_uint32), ("first_mask", ctypes.c_uint32), ("t_max", ctypes.c_float), ("sun_dir", ctypes.c_float * 3),
+                        ("fog_start", ctypes.c_float), ("fog_end", ctypes.c_float), ("sky_rgb", ctypes.c_uint8 * 3), ("sun_level", ctypes.c_uint8),
+                        ("shadow_dim", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3)]
+        f3, b3 = ctypes.c_float * 3, ctypes.c_uint8 * 3
+        cam = Camera(f3(*eye), f3(*forward), f3(*up), fov_y, width, height)
+        par = Params(flags, first_mask, t_max, f3(*sun_dir), fog_start, fog_end, b3(*sky_rgb), sun_level, shadow_dim)
+        vp, i32 = ctypes.c_void_p, ctypes.c_int
+        self.lib.mmgen_render_camera.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, ctypes.POINTER(Camera), ctypes.POINTER(Params), vp, vp, vp]
+        assert grid.dtype == t.int32 and grid.is_contiguous()
+        assert palette is None or (palette.element_size() == 4 and palette.numel() == 256 and palette.is_contiguous())
+        rgba = self._empty((height, width, 4), t.uint8)
+        hits = self._empty((height, width, 5), t.int32) if return_hits else None
+        self._check(self.lib.mmgen_render_camera(self._p(blocks), self._p(grid), grid.shape[1], grid.shape[0], self._p(occ_first), self._p(occ_second),
+                                                 self._p(light), self._p(palette), ctypes.byref(cam), ctypes.byref(par), self._p(rgba), self._p(hits),
+                                                 self._stream()), "mmgen_render_camera")
+        return (rgba, hits) if return_hits else rgba
+
     @classmethod
     def ray_hits(cls, hits):
         """The int32 [..., 5] tensor of raycast / render_view as a numpy record array [...] of mmgen_ray_hit."""

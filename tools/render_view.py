@@ -5,12 +5,15 @@ block id, face and shadow, and writes <out>.ppm (binary P6) and <out>.npy (the h
 
 usage: tools/render_view.py [--cx 1488 --cz -1110 --nx 8 --nz 8] [--eye surface|cave|x,y,z] [--forward x,y,z] [--size 1280x720] [--out view]
        tools/render_view.py --light ...   # shade by the light volume (mmgen_light): max(sky, block) / 15 of the voxel in front of the hit face
-       tools/render_view.py --measure     # both eyes, skip / no-skip, occupancy build, visits per ray
+       tools/render_view.py --device ...  # the whole image on the device (mmgen_render_camera): light, AO, water, sun shadow, fog
+       tools/render_view.py --measure     # both eyes, skip / no-skip, occupancy build, visits per ray; section 6.13: the
+                                          # host-shaded path against mmgen_raycast_camera alone and mmgen_render_camera (--warmup, --reps)
 Eye and forward are in grid-local block coordinates (x, z from the region's corner, y = world y)."""
 import argparse
 import importlib
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -115,6 +118,43 @@ def timed(gen, fn, warmup=10, reps=200):
     return float(np.median(ms)), min(ms), max(ms)
 
 
+def wall_ms(gen, fn, warmup, reps):
+    """milliseconds per call on the host clock, the device idle before and after each call (a path that ends in numpy has no device event
+    at its end): median, min, max"""
+    sync = gen.torch.cuda.synchronize
+    ms = []
+    for k in range(warmup + reps):
+        sync(); t0 = time.perf_counter(); fn(); sync()
+        ms.append(1e3 * (time.perf_counter() - t0))
+    ms = ms[warmup:]
+    return float(np.median(ms)), min(ms), max(ms)
+
+
+def device_kwargs(gen, blocks, grid, flags):
+    """what mmgen_render_camera needs beside the first occupancy: the occupancy of OPAQUE | SEMI and the light volume"""
+    return dict(occ_second=gen.ray_occupancy(blocks, 3), light=gen.light(gen.light_masks(blocks), grid), flags=flags, sun_dir=tuple(float(c) for c in SUN),
+                fog_start=200.0, fog_end=1500.0, sky_rgb=tuple(int(c) for c in SKY))
+
+
+def measure_render(gen, args, blocks, grid, occ, eye, forward, w, h):
+    """the host-shaded path of this tool (camera kernel, read-back, numpy shading, shadow-ray call) against the camera
+    kernel alone and the shaded render with no flag and with all four, one process, the same warm-up and repeats for each"""
+    cam = dict(eye=eye, forward=forward, fov_y=1.0, width=w, height=h, t_max=4096.0)
+    dirs = pixel_dirs(forward, (0.0, 1.0, 0.0), 1.0, w, h)
+    dev = device_kwargs(gen, blocks, grid, 15)
+    paths = (("host path: camera + read-back + numpy shading + shadow rays", lambda: shade(gen, blocks, grid, occ, gen.render_view(blocks, grid, occ, **cam), eye, dirs, 4096.0)),
+             ("mmgen_raycast_camera alone", lambda: gen.render_view(blocks, grid, occ, **cam)),
+             ("mmgen_render_camera flags 0", lambda: gen.render_camera(blocks, grid, occ, **dict(cam, **dict(dev, flags=0)))),
+             ("mmgen_render_camera all flags", lambda: gen.render_camera(blocks, grid, occ, **dict(cam, **dev))))
+    res = {}
+    for name, fn in paths:
+        res[name] = wall_ms(gen, fn, args.warmup, args.reps)
+        print(f"render {w}x{h}, eye ({eye[0]:.1f}, {eye[1]:.1f}, {eye[2]:.1f}): {name:62s} median {res[name][0]:9.3f} ms (min {res[name][1]:.3f}, max {res[name][2]:.3f}) "
+              f"over {args.reps} runs after {args.warmup}")
+    m = [res[name][0] for name, _ in paths]
+    print(f"render flags 0 / camera alone = {m[2] / m[1]:.3f}; host path / render all flags = {m[0] / m[3]:.1f}")
+
+
 def measure(gen, args):
     nx = nz = 32
     w, h = 1280, 720
@@ -139,6 +179,7 @@ def measure(gen, args):
         same = all(np.array_equal(res["skip"][1][f], res["no_skip"][1][f]) for f in ("voxel", "block", "face", "status")) and \
             np.array_equal(res["skip"][1]["t"].view(np.uint32), res["no_skip"][1]["t"].view(np.uint32))
         print(f"{kind:8s} no_skip / skip = {res['no_skip'][0] / res['skip'][0]:.2f}x, images identical: {same}")
+        measure_render(gen, args, blocks, grid, occ, eye, forward, w, h)
 
 
 def main():
@@ -148,6 +189,8 @@ def main():
     ap.add_argument("--eye", default="surface"); ap.add_argument("--forward", default="1,-0.35,0.6")
     ap.add_argument("--fov", type=float, default=1.0); ap.add_argument("--size", default="1280x720")
     ap.add_argument("--out", default="view"); ap.add_argument("--measure", action="store_true")
+    ap.add_argument("--device", action="store_true", help="shade on the device: the PPM is the output of mmgen_render_camera with all four flags")
+    ap.add_argument("--warmup", type=int, default=5); ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--light", action="store_true", help="shade by the light volume (sky and block light) instead of face factor and shadow ray")
     args = ap.parse_args()
     gen = importlib.import_module("mega-minecraft_amd").MMGen(0)
@@ -159,10 +202,15 @@ def main():
     occ = gen.ray_occupancy(blocks, 15)
     eye = eye_for(args.eye, blocks.cpu().numpy(), args.nx, args.nz) if args.eye in ("surface", "cave") else tuple(float(v) for v in args.eye.split(","))
     forward = tuple(float(v) for v in args.forward.split(","))
-    hits = gen.render_view(blocks, grid, occ, eye, forward, fov_y=args.fov, width=w, height=h, t_max=4096.0)
-    if args.light:
+    if args.device:
+        rgba, hits = gen.render_camera(blocks, grid, occ, eye, forward, fov_y=args.fov, width=w, height=h, t_max=4096.0, return_hits=True,
+                                       **device_kwargs(gen, blocks, grid, 15))
+        img, H = np.ascontiguousarray(rgba.cpu().numpy()[..., :3]), gen.ray_hits(hits)
+    elif args.light:
+        hits = gen.render_view(blocks, grid, occ, eye, forward, fov_y=args.fov, width=w, height=h, t_max=4096.0)
         img, H = shade_by_light(gen, hits, gen.light(gen.light_masks(blocks), grid).cpu().numpy(), grid.cpu().numpy())
     else:
+        hits = gen.render_view(blocks, grid, occ, eye, forward, fov_y=args.fov, width=w, height=h, t_max=4096.0)
         img, H = shade(gen, blocks, grid, occ, hits, eye, pixel_dirs(forward, (0.0, 1.0, 0.0), args.fov, w, h), 4096.0)
     with open(args.out + ".ppm", "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (w, h)); f.write(img.tobytes())
